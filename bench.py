@@ -1,7 +1,14 @@
 """Headline benchmark: exact top-10 queries/sec over 10M x 1536 fp32 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5]
-                    [--ntotal N] [--batch B] [--k K] [--metric ip|l2] [--no-cpu-baseline]
+                    [--ntotal N] [--batch B] [--k K] [--metric ip|l2]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline ...]]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(with the roofline of the timed steps' own kernel, which costs no run of its
+own).  --dump-outputs DIR then writes what the last timed step returned as
+DIR/<name>.npy.  Every other leg (the live fp32-engine check, batch 1, wide k,
+any k, the clustered corpus, the CPU baseline, C5's recall) runs with --full.
 
 Ranks: under torchrun (WORLD_SIZE set) this process is one rank.  Started
 directly with --gpus N > 1, it is a launcher: it starts N fresh rank processes
@@ -23,7 +30,8 @@ Workloads (BASELINE.json configs; the default is the one the metric is quoted on
 Corpus and queries are generated on the device by the counter-based generator
 (no dataset exists offline) and are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields:
+Rank 0 prints ONE JSON line.  Besides the driver's fields (the records after
+`roofline` are measured with --full only and are null without it):
   roofline      the dominant kernel: algorithmic work per launch (FLOP for the
                 MFMA kernels, bytes for the HBM-bound GEMV) / mean launch time from
                 HIP events recorded on the launch stream (vs_timer_*), against the
@@ -175,6 +183,14 @@ def parse(argv=None):
     p.add_argument("--cpu-queries", type=int, default=1024)
     p.add_argument("--recall-queries", type=int, default=1000)
     p.add_argument("--cpu-batch1-rows", type=int, default=1_000_000)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run every other leg: the live fp32-engine "
+                        "check of the timed lists, batch 1, wide k, any k, the clustered "
+                        "corpus, the CPU baseline (c2/c3), C5's recall; off by default")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy (float32 "
+                        "scores, labels as float64; at most 64 MB in all: a fixed seeded "
+                        "sample of the rows, listed in rows.npy, where the lists are larger)")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher/collective rehearsal on CPU (gloo, no GPU, no kernel): "
                         "each step all-gathers a (batch, k) list like the sharded search; "
@@ -438,6 +454,41 @@ class Ctx:
         return self.max_over_ranks(t1 - t0), kms, nl, last
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # of --dump-outputs' 64 MB, all files together
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: `arrays` maps a name to what the timed path returned in
+    its last step (torch tensors with one row per query, on any device).
+    Floating-point arrays are stored as float32, integer ones as float64
+    (labels are far below 2^53).  Where the whole would pass the budget, the
+    same rows of every array are kept: a sorted sample drawn with a fixed seed,
+    stored as rows.npy."""
+    import numpy as np
+    import torch
+
+    nrows = min(int(a.shape[0]) for a in arrays.values())
+    row_bytes = 0
+    for a in arrays.values():
+        per = 1
+        for n in a.shape[1:]:
+            per *= int(n)
+        row_bytes += per * (4 if a.dtype.is_floating_point else 8)
+    keep = None
+    if nrows * row_bytes > DUMP_BUDGET_BYTES:
+        nkeep = max(1, DUMP_BUDGET_BYTES // (row_bytes + 8))
+        keep = np.sort(np.random.default_rng(2024).choice(nrows, nkeep, replace=False))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        if keep is not None:
+            a = a[torch.from_numpy(keep).to(a.device)]
+        a = a.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    if keep is not None:
+        np.save(os.path.join(dirpath, "rows.npy"), keep.astype(np.float64))
+
+
 def dump_record(d, o):
     """The filter pass's dump launches over the timed steps (vs_gemm_x1.hip
     header): rows stored below the lists' floors (one (row, raw sum) slot
@@ -600,8 +651,10 @@ def run_knn(args, ctx):
     flops = 2.0 * n_shard * d * B
     esz = 4 if args.dtype == "f32" else 2
     kname = ctx.lib.timer_kernel()
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, {"D": D, "I": I})
     exact_check = None
-    if is_x1(kname):
+    if args.full and is_x1(kname):
         # the same queries through the exact fp32 MFMA engine: ids must agree up to
         # exact fp32 near-ties (the verify step makes the filter engine exact; this
         # re-checks it live; the two round their fp32 scores differently)
@@ -644,7 +697,7 @@ def run_knn(args, ctx):
             rf["first_stage_planes"] = split
 
     batch1 = None
-    if args.batch1_steps > 0 and not gemv:
+    if args.full and args.batch1_steps > 0 and not gemv:
         q1 = xq[:1].contiguous()
         t1, k1, n1, _ = ctx.timed(lambda i: index.search_device(q1, k, stream=ctx.stream),
                                   args.batch1_steps, 3)
@@ -686,8 +739,8 @@ def run_knn(args, ctx):
     # engine only for what the filter cannot settle).  Measured apart so that
     # each k has a number beside the headline; not part of `value`.
     wide = None
-    if (args.wide_k_steps > 0 and metric == vfaiss.METRIC_INNER_PRODUCT and args.wide_k
-            and not gemv):
+    if (args.full and args.wide_k_steps > 0 and metric == vfaiss.METRIC_INNER_PRODUCT
+            and args.wide_k and not gemv):
         wide = []
         bw = min(args.wide_k_batch, B)
         qw = xq[:bw].contiguous()
@@ -725,7 +778,7 @@ def run_knn(args, ctx):
     # engine (vs_api.hip run_paged), at batch 1 (the live tool) and at the full
     # batch.  Measured apart; not part of `value`.
     anyk = None
-    if args.any_k > 0 and not gemv:
+    if args.full and args.any_k > 0 and not gemv:
         anyk = []
         for bk, steps in ((1, 3), (B, 1)):
             qk = xq[:bk].contiguous()
@@ -751,7 +804,7 @@ def run_knn(args, ctx):
 
     if ctx.rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and ctx.world == 1 and args.dtype == "f32":
+        if args.full and not args.no_cpu_baseline and ctx.world == 1 and args.dtype == "f32":
             cpu = cpu_baseline(index.shard, args, xq.cpu().numpy())
         res = base_result(args, ctx, args.steps * B / elapsed, elapsed)
         if args.data == "clustered":
@@ -856,7 +909,7 @@ def run_selfjoin(args, ctx):
     flops_step = 2.0 * N * d * nq
     kname = ctx.lib.timer_kernel()
     exact_check = None
-    if is_x1(kname):
+    if args.full and is_x1(kname):
         # the first 256 students again through the fp32 MFMA engine: ids must agree
         nchk = min(nq, 256)
         De = torch.empty((nchk, k), dtype=torch.float32, device="cuda")
@@ -901,6 +954,8 @@ def run_selfjoin(args, ctx):
         writer = {"rows_gathered_on_rank0": int(Sall.shape[0]),
                   "edges_sim_ge_0.75": int(((Iall >= 0) & (Sall >= 0.75)).sum().item()),
                   "edges_total": int((Iall >= 0).sum().item())}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"D": Sall, "I": Iall})
         res = base_result(args, ctx, args.steps * N / elapsed, elapsed, unit="students/s")
         res["config"] = {"workload": f"C4: self-join {N}x{d} cosine top-{k} excluding self",
                          "ntotal": N, "d": d, "k": k,
@@ -970,7 +1025,9 @@ def run_c5(args, ctx):
         j = (max(i, 0) * B) % (xq.shape[0] - B + 1)
         return index.search_device(xq[j:j + B], k, stream=ctx.stream)
 
-    elapsed, kms, nl, _ = ctx.timed(step, args.steps, args.warmup)
+    elapsed, kms, nl, (Dl, Il) = ctx.timed(step, args.steps, args.warmup)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, {"D": Dl, "I": Il})
     gen = np.arange(N, dtype=np.int64)  # generator row of every current label
     for r, rm in enumerate(done):
         g0 = N + r * nmut
@@ -988,7 +1045,7 @@ def run_c5(args, ctx):
                   f"{n_shard}*{d}*{esz} B per search (batch {B} over the rank's shard)",
                   kname, traffic, tsrc)
     recall = None
-    if ctx.world == 1 and args.recall_queries > 0:
+    if args.full and ctx.world == 1 and args.recall_queries > 0:
         nr = args.recall_queries
         q = xq[:nr].contiguous()
         Dg, Ig = index.search_device(q, k, stream=ctx.stream)
@@ -1058,6 +1115,8 @@ def run_dry(args, ctx):
     outs = [torch.empty_like(D) for _ in range(ctx.world)]
     elapsed, _, _, _ = ctx.timed(lambda i: ctx.dist.all_gather(outs, D), args.steps, args.warmup)
     if ctx.rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"gathered": torch.stack(outs)})
         res = base_result(args, ctx, args.steps * B / elapsed, elapsed)
         res["dry_run"] = True
         res["data"] = "none: dry run (gloo all-gather of a (batch, 2k-1) list per step, no kernel)"
@@ -1076,7 +1135,7 @@ def main():
         res = run_dry(args, ctx)
     elif args.workload in ("c3", "c2"):
         res = run_knn(args, ctx)
-        if (args.workload == "c3" and args.data == "uniform" and ctx.world == 1
+        if (args.full and args.workload == "c3" and args.data == "uniform" and ctx.world == 1
                 and args.clustered_steps > 0 and args.dtype == "f32"):
             # embedding-like rows beside the uniform headline (the headline's
             # index is gone with run_knn's frame): same shape, same engine
@@ -1087,6 +1146,7 @@ def main():
             ca = copy.copy(args)
             ca.data, ca.steps, ca.warmup = "clustered", args.clustered_steps, 1
             ca.batch1_steps, ca.wide_k_steps, ca.any_k, ca.no_cpu_baseline = 0, 0, 0, True
+            ca.dump_outputs = None  # the dump is the headline's
             cres = run_knn(ca, ctx)
             if res is not None and cres is not None:
                 res["clustered"] = clustered_record(cres)

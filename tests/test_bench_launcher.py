@@ -44,3 +44,47 @@ def test_bench_single_rank_no_launcher():
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert res["n_gpus"] == 1 and res["ranks_seen"] == 1
+
+
+def test_bench_options_full_and_dump_outputs():
+    """--full is off by default and --dump-outputs takes a directory; --steps is
+    the number of timed steps the line reports."""
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None
+    assert a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_formats_and_budget(tmp_path):
+    """Scores are stored as float32 and labels as float64, unchanged in value;
+    past the budget the same seeded sample of rows is kept of every array and
+    rows.npy names them, the same rows on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    D = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    I = torch.arange(12, dtype=torch.int64).reshape(4, 3) + (1 << 40)
+    bench.dump_outputs(str(tmp_path / "a"), {"D": D, "I": I})
+    Dn, In = np.load(tmp_path / "a" / "D.npy"), np.load(tmp_path / "a" / "I.npy")
+    assert Dn.dtype == np.float32 and In.dtype == np.float64
+    assert (Dn == D.numpy()).all() and (In.astype(np.int64) == I.numpy()).all()
+    assert not (tmp_path / "a" / "rows.npy").exists()
+
+    n = bench.DUMP_BUDGET_BYTES // (4 * 4 + 8) * 2  # twice the budget
+    D = torch.arange(n * 4, dtype=torch.float32).reshape(n, 4)
+    I = torch.arange(n, dtype=torch.int64)
+    total = 0
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), {"D": D, "I": I})
+        total = sum(f.stat().st_size for f in (tmp_path / name).iterdir())
+        assert total <= 64 * 10 ** 6
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert (rows == np.load(tmp_path / "c" / "rows.npy")).all()
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n
+    assert (np.load(tmp_path / "b" / "I.npy") == rows).all()
+    assert (np.load(tmp_path / "b" / "D.npy")[:, 0] == D[:, 0].numpy()[rows.astype(np.int64)]).all()

@@ -69,7 +69,7 @@ def test_bench_world2_knn_on_one_gpu():
     tolerance, and rank 0 reports the world the collective saw."""
     res = _run_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c2",
                       "--ntotal", "200000", "--batch", "1024", "--steps", "2", "--warmup", "1",
-                      "--batch1-steps", "0", "--wide-k-steps", "2", "--no-cpu-baseline"],
+                      "--full", "--batch1-steps", "0", "--wide-k-steps", "2", "--no-cpu-baseline"],
                      2, 100, _BENCH_ENV)
     assert res["n_gpus"] == 2 and res["ranks_seen"] == 2
     assert res["result_sane"] is True
@@ -82,7 +82,8 @@ def test_bench_world2_selfjoin_split_and_gather():
     """C4 at N = 2 (reduced): each rank self-joins its block of students over
     the replicated corpus; the rows are gathered to rank 0 (the writer)."""
     res = _run_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4",
-                      "--ntotal", "60000", "--steps", "2", "--warmup", "1"], 2, 100, _BENCH_ENV)
+                      "--ntotal", "60000", "--steps", "2", "--warmup", "1", "--full"],
+                     2, 100, _BENCH_ENV)
     assert res["n_gpus"] == 2 and res["result_sane"] is True
     assert res["writer"]["rows_gathered_on_rank0"] == 60000
     assert res["writer"]["edges_total"] == 60000 * 50

@@ -12,7 +12,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 PYT="python3 -u -m pytest -x -v --timeout 300 --timeout-method thread"
-BENCH="python3 -u bench.py"
+BENCH="python3 -u bench.py --full"
 for st in "$@"; do
   echo "== $st $(date +%T)"
   case $st in
