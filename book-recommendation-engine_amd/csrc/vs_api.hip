@@ -903,6 +903,16 @@ static bool dump_enabled() {
   return v;
 }
 
+// Query cuts taken again after every replay of a cutting pass (default; env
+// VS_X1_RECUT=0 sets them once, after the list launch; 2 refreshes them with
+// the separate replay and cut kernels instead of the fused one; A/B, read at
+// every search)
+static int recut_mode() {
+  const char* e = getenv("VS_X1_RECUT");
+  const int v = e ? atoi(e) : 1;
+  return v == 0 ? 0 : v == 2 ? 2 : 1;
+}
+
 // Small batches through the staged engine's skinny passes (env
 // VS_SMALL_FILTER=0 keeps the exact streaming kernels, for A/B; read at every
 // search), over indexes of at least kSmallFilterMinRows rows.
@@ -1171,6 +1181,7 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
         x.qbkey = bk;
         x.qcut_m = need;
         x.dump = true;
+        x.recut = recut_mode();
         x.dcount = dc;
         x.dslot = ds;
         x.dR = dR;

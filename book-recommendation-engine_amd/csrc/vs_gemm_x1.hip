@@ -36,7 +36,8 @@
 //  * dump launches (every later launch of an int8 or bf16 inner-product
 //    pass): the lists stay in memory; the epilogue compares each block with
 //    its list's floor (the query's CUT, x1_qcut, set from the first launch's
-//    lists, or the list's own last entry) and, for the rare block that may
+//    lists and taken again after every replay, or the list's own last entry)
+//    and, for the rare block that may
 //    hold a row below it, stores one (row, raw sum) pair per row that clears
 //    the per-row threshold to the list's next dump slot; x1_replay (between
 //    segments of launches) admits the dumped rows into the lists exactly as a
@@ -1303,6 +1304,7 @@ static int x1_qg() {
 }
 
 static hipError_t launch_qcut(const X1Args& a, Partials part, hipStream_t st);
+static hipError_t launch_x1_replay_cut(const X1Args& a, Partials part, hipStream_t st);
 
 // XCD rounds of query-tile groups for grids of more than 8 groups (env
 // VS_X1_XCDG=0 turns them off, for A/B; read at every search)
@@ -1485,8 +1487,17 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
     // by ~8 of the next n) — the cut alone is too wide when 2B spans
     // thousands of rows (C3: ~5k, 63 % of the lists out of 32 slots in one
     // segment, profiles/r04b).
+    //
+    // The cuts again after every replay of a cutting pass but the last (a.recut;
+    // "Query cuts" below): the lists hold better keys than when the cut was
+    // taken, a_M has only fallen, and min(old cut, a_M(now) + 2B) is a valid
+    // cut for the segments that follow (C3: the cut from 1/20 of the corpus let
+    // 2.8k rows per query through, most of them in the later, longer segments).
+    // After the last replay nothing reads a new cut but the verification,
+    // which takes a_M + 2B itself.
     if (later_dump && c > 0 && (sseg || ((c + 1) & c) == 0 || c + 1 == nlaunch)) {
-      e = launch_x1_replay(a, part, st);
+      e = cutting && a.recut && c + 1 < nlaunch ? launch_x1_replay_cut(a, part, st)
+                                                : launch_x1_replay(a, part, st);
       if (e != hipSuccess) return e;
     }
   }
@@ -2842,6 +2853,12 @@ hipError_t launch_verify_wide(int mode, int nq_max, const int* qlist, const int*
 // the cut is the M-th best over all of them plus 2B, so a dump launch finds a
 // block below it only for ~1 in 40 (lane, block) pairs — rare enough that a
 // wave almost never waits on one (tests/test_filter_argument.py models it).
+// The cut is taken again after every replay but the last (x1_replay_cut_kernel
+// below, env VS_X1_RECUT): cut[q] = min(cut[q], a_M(lists after the replay) +
+// 2.000001 B).  It never rises, -FLT_MAX stays, a query with fewer than M
+// entries gets none, and every value it ever held is >= the final a_M + 2B, so
+// the final cut is a floor for every row any launch dropped
+// (tests/test_cut_refresh_argument.py).
 
 // bkey[q]: the bound B of query q (bound_key over its split norms, the same
 // double the verification computes).
@@ -3189,6 +3206,183 @@ __global__ __launch_bounds__(kQcutThreads) void qcut_kernel(
   }
 }
 
+// The replay of a segment and the query's next cut in one kernel (the cuts
+// taken again after every replay, x1_launch): one workgroup per query, thread t
+// the query's lane list t (P <= 256 lists; the slots of consecutive lists are
+// consecutive in every slot plane, so a wave's slot reads are whole lines as
+// in x1_replay_kernel).  Each thread replays its list exactly as
+// x1_replay_kernel does — the same x1_key expression, the same admission
+// against min(last entry, the cut the segment's launches ran with), the same
+// overflow rule — and keeps it in registers; the workgroup then finds a_M, the
+// M-th smallest key over the P lists, by a radix select over the four bytes of
+// the order image (a 256-bin histogram per byte: 4 rounds instead of the
+// bitwise search's 32) and writes the cut as qcut_kernel does.  What keeps the
+// pass exact:
+//  * the cut never rises: it is written only when below the stored value;
+//  * a cut of -FLT_MAX (a list of the query out of slots, now or in an earlier
+//    segment) stays -FLT_MAX: nothing is below it, and the selection is skipped;
+//  * fewer than M entries over the lists: no cut is written;
+//  * a_M only falls while the pass runs, so every cut ever written is >= the
+//    final a_M + 2B: a row dropped at launch c had key >= min(cut_c, last_c) >=
+//    min(final cut, final last), which is the floor the verification takes
+//    (T = min(T, cut)), and the verification itself uses nothing above a_M + 2B.
+template <int KR, int EL>
+__global__ __launch_bounds__(256) void x1_replay_cut_kernel(
+    int* __restrict__ dcount, const int* __restrict__ dslot, float* __restrict__ pkey,
+    int* __restrict__ pid, int P, int KP, const float* __restrict__ qs,
+    const float* __restrict__ xs, int64_t self0, int ntotal, int dR, int64_t nl,
+    float* __restrict__ qcut, unsigned long long* __restrict__ stats, int M,
+    const double* __restrict__ bkey) {
+  __shared__ int hist[256];
+  __shared__ int wsum[4];
+  __shared__ int s_over, sel_digit, sel_before;
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nth = blockDim.x, nwv = nth >> 6;
+  const bool has = tid < P;
+  const int64_t i = (int64_t)q * P + tid;
+  const int cnt = has ? dcount[i] : 0;
+  {  // statistics: one atomic per wave
+    unsigned long long a = (unsigned long long)cnt, b = cnt > dR ? 1ull : 0ull;
+    for (int o = 32; o > 0; o >>= 1) {
+      a += __shfl_xor(a, o);
+      b += __shfl_xor(b, o);
+    }
+    if (lane == 0 && a && stats) {
+      atomicAdd(stats, a);
+      if (b) atomicAdd(stats + 1, b);
+    }
+  }
+  if (tid == 0) s_over = 0;
+  // the cut the segment's launches ran with (written again only at the end,
+  // after every thread has read it)
+  const float cut = qcut[q];
+  static_assert(KR % 4 == 0, "lane lists move as 16-B pieces");
+  float lk[KR];
+  int li[KR];
+  const int64_t o = i * KP;  // KP: a multiple of 4 (launch_x1_replay_cut)
+#pragma unroll
+  for (int e = 0; e < KR; ++e) lk[e] = FLT_MAX, li[e] = -1;
+  if (has) {
+#pragma unroll
+    for (int e = 0; e < KR; e += 4) {
+      const f32x4 kv = *(const f32x4*)(pkey + o + e);
+      const int4 iv = *(const int4*)(pid + o + e);
+      lk[e] = kv.x, lk[e + 1] = kv.y, lk[e + 2] = kv.z, lk[e + 3] = kv.w;
+      li[e] = iv.x, li[e + 1] = iv.y, li[e + 2] = iv.z, li[e + 3] = iv.w;
+    }
+  }
+  __syncthreads();  // s_over is zero before any list reports
+  if (cnt > 0) {
+    dcount[i] = 0;  // the next segment's dumps start at slot 0
+    if (cnt > dR) {
+      s_over = 1;  // the list lost rows: its query fails (below)
+    } else {
+      const float qsc = EL == FILTER_I8 ? qs[q] : 0.0f;
+      const int selfrow = self0 >= 0 ? (int)(self0 + q) : -1;
+      const i32x2* sl = (const i32x2*)dslot + i;
+      constexpr int kB = 8;
+      for (int c0 = 0; c0 < cnt; c0 += kB) {
+        i32x2 e[kB];
+        float fx[kB];
+#pragma unroll
+        for (int j = 0; j < kB; ++j)
+          e[j] = c0 + j < cnt ? sl[(int64_t)(c0 + j) * nl] : i32x2{-1, 0};
+#pragma unroll
+        for (int j = 0; j < kB; ++j)
+          fx[j] = EL == FILTER_I8 && e[j][0] >= 0 && e[j][0] < ntotal ? xs[e[j][0]] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < kB; ++j) {
+          const int row = e[j][0];
+          if (!(row >= 0 && row < ntotal && row != selfrow)) continue;
+          const float key = x1_key<EL>(e[j][1], qsc, fx[j]);
+          if (key < fminf(lk[KR - 1], cut)) list_insert<KR, int>(lk, li, key, row);
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < KR; e += 4) {
+        *(f32x4*)(pkey + o + e) = f32x4{lk[e], lk[e + 1], lk[e + 2], lk[e + 3]};
+        *(int4*)(pid + o + e) = make_int4(li[e], li[e + 1], li[e + 2], li[e + 3]);
+      }
+    }
+  }
+  __syncthreads();
+  if (s_over) {  // uniform
+    if (tid == 0) qcut[q] = -FLT_MAX;
+    return;
+  }
+  if (cut == -FLT_MAX) return;  // uniform: failed in an earlier segment, stays failed
+  // order images of the thread's entries (empty entries are never counted)
+  uint32_t v[KR];
+  int nv = 0;
+#pragma unroll
+  for (int e = 0; e < KR; ++e) {
+    v[e] = key_order(lk[e]);
+    nv += li[e] >= 0 ? 1 : 0;
+  }
+  for (int o2 = 32; o2 > 0; o2 >>= 1) nv += __shfl_xor(nv, o2);
+  if (lane == 0) wsum[wv] = nv;
+  __syncthreads();
+  int total = 0;
+  for (int w2 = 0; w2 < nwv; ++w2) total += wsum[w2];
+  if (total < M) return;  // uniform: fewer than M entries, no cut yet
+  // the M-th smallest image: per byte from the top, the histogram of the
+  // entries that share the bytes chosen so far and the bin where the running
+  // count reaches the rank left (duplicates share a bin to the end)
+  uint32_t pre = 0;
+  int want = M;
+  for (int sh = 24; sh >= 0; sh -= 8) {
+    for (int b = tid; b < 256; b += nth) hist[b] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < KR; ++e)
+      if (li[e] >= 0 && (sh == 24 || (v[e] >> (sh + 8)) == (pre >> (sh + 8))))
+        atomicAdd(&hist[(v[e] >> sh) & 0xFF], 1);
+    __syncthreads();
+    if (wv == 0) {  // the bin where the running count reaches `want`
+      const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2],
+                h3 = hist[4 * lane + 3];
+      const int own = h0 + h1 + h2 + h3;
+      int inc = own;  // inclusive prefix over the lanes
+      for (int o2 = 1; o2 < 64; o2 <<= 1) {
+        const int t = __shfl_up(inc, o2);
+        if (lane >= o2) inc += t;
+      }
+      const int before = inc - own;
+      if (before < want && want <= inc) {
+        int c = before, d = 4 * lane;
+        const int hh[4] = {h0, h1, h2, h3};
+        for (int e = 0; e < 4; ++e) {
+          if (c + hh[e] >= want) {
+            d = 4 * lane + e;
+            break;
+          }
+          c += hh[e];
+        }
+        sel_digit = d;
+        sel_before = c;
+      }
+    }
+    __syncthreads();
+    pre |= (uint32_t)sel_digit << sh;
+    want -= sel_before;
+    // (the next round's first barrier separates these reads from the next
+    // writes of sel_digit / sel_before; hist is rewritten before it, but only
+    // wave 0 read it, before the barrier above)
+  }
+  if (tid == 0) {
+    const float aM = key_unorder(pre);
+    const double tp = (double)aM + 2.000001 * bkey[q];
+    if (isfinite(tp) && tp < (double)FLT_MAX) {
+      float t = (float)tp;
+      if ((double)t < tp) t = nextafterf(t, INFINITY);
+      if (t < cut) qcut[q] = t;
+    }
+  }
+}
+
+constexpr int kReplayCutMaxP = 256;
+
 hipError_t launch_qbound(int mode, const float* Q, int64_t ld, const float* qn, int filter,
                          const unsigned* stats, const float* qr2i8, int nq, double* bkey,
                          hipStream_t st, const BoundArgs* bap) {
@@ -3213,6 +3407,29 @@ static hipError_t launch_qcut(const X1Args& a, Partials part, hipStream_t st) {
   const int nq = a.nqa;
   hipLaunchKernelGGL(qcut_kernel, dim3(nq), dim3(kQcutThreads), 0, st, part.key, part.id, part.P, part.KP,
                      x1_lane_len(), a.qcut_m, a.qbkey, nq, a.qcut);
+  return hipGetLastError();
+}
+
+// The replay of a segment and the cuts after it (a cutting pass, x1_launch):
+// the fused kernel for up to kReplayCutMaxP lists per query, else (or with
+// a.recut == 2, the A/B of the fusion) x1_replay and x1_qcut back to back.
+static hipError_t launch_x1_replay_cut(const X1Args& a, Partials part, hipStream_t st) {
+  if (!a.dump || !a.dcount || a.nqa <= 0) return hipSuccess;
+  if (part.KP < x1_lane_len() || part.KP % 4 != 0) return hipErrorInvalidValue;
+  if (a.recut == 2 || part.P > kReplayCutMaxP) {
+    const hipError_t e = launch_x1_replay(a, part, st);
+    return e != hipSuccess ? e : launch_qcut(a, part, st);
+  }
+  const int64_t nl = (int64_t)a.nq_pad * part.P;  // lists of the pass (the slots' stride)
+  const dim3 block((unsigned)((part.P + 63) / 64 * 64));
+  if (a.filter == FILTER_I8)
+    hipLaunchKernelGGL((x1_replay_cut_kernel<8, FILTER_I8>), dim3(a.nqa), block, 0, st, a.dcount,
+                       a.dslot, part.key, part.id, part.P, part.KP, a.qs, a.xs, a.self0, a.ntotal,
+                       a.dR, nl, a.qcut, a.dstats, a.qcut_m, a.qbkey);
+  else
+    hipLaunchKernelGGL((x1_replay_cut_kernel<8, FILTER_BF16>), dim3(a.nqa), block, 0, st, a.dcount,
+                       a.dslot, part.key, part.id, part.P, part.KP, a.qs, a.xs, a.self0, a.ntotal,
+                       a.dR, nl, a.qcut, a.dstats, a.qcut_m, a.qbkey);
   return hipGetLastError();
 }
 

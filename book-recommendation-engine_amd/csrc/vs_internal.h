@@ -133,6 +133,7 @@ struct X1Args {
   float* qcut = nullptr;         // per query (nqa): the cut, set after the first launch
   const double* qbkey = nullptr; // per query: the verification's bound B (x1_qcut)
   int qcut_m = 0;                // the M of the verification
+  int recut = 1;                 // cuts after every replay: 0 set once, 1 fused, 2 replay + x1_qcut
   int* dcount = nullptr;         // [nq_pad][P] dumps per lane list (zeroed before the pass)
   int* dslot = nullptr;          // [nq_pad][P][dR][2] dumped (row, raw sum) pairs
   int dR = 0;                    // dump slots per lane list and segment

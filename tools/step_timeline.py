@@ -6,6 +6,7 @@ one search.
     rocprofv3 --kernel-trace --output-format csv -d OUT -o run -- \
         python3 tools/step_timeline.py --n 1000000 --b 1024
     python3 tools/step_timeline.py --report OUT/.../run_kernel_trace.csv
+    python3 tools/step_timeline.py --report <bench.py's kernel trace> --last-search
 """
 import argparse
 import csv
@@ -17,25 +18,58 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "book-recommendation-engine_amd"))
 
 
-def report(path, gap_ms=100.0):
+def x1_launch_kind(name):
+    """'list' / 'dump' for a gemm_topk_x1<KR, MODE, DUMP, EL, ..> launch, else None."""
+    head = name.split("(")[0]
+    if "gemm_topk_x1<" not in head:
+        return None
+    args = [a.strip() for a in head[head.find("<") + 1:].split(",")]
+    return "dump" if len(args) > 2 and args[2] == "true" else "list"
+
+
+def report(path, gap_ms=100.0, last_search=False):
     rows = list(csv.DictReader(open(path)))
     ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows)
-    cut = 0
-    for i in range(1, len(ev)):
-        if ev[i][0] - ev[i - 1][1] > gap_ms * 1e6:
-            cut = i
-    ev = ev[cut:]
+    if last_search:
+        # a bench.py trace (no sleep between searches): the last full-size list
+        # launch, back to the query plane's conversion before it, on to the
+        # search's closing counter kernel
+        idx = max(i for i, e in enumerate(ev) if x1_launch_kind(e[2]) == "list"
+                  and e[1] - e[0] > 1e6)
+        first = max(i for i in range(idx) if "quantize_i8_kernel" in ev[i][2]
+                    or "bf16_plane_kernel" in ev[i][2])
+        last = next(i for i in range(idx, len(ev)) if "add_counts_kernel" in ev[i][2])
+        ev = ev[first:last + 1]
+    else:
+        cut = 0
+        for i in range(1, len(ev)):
+            if ev[i][0] - ev[i - 1][1] > gap_ms * 1e6:
+                cut = i
+        ev = ev[cut:]
     t0 = ev[0][0]
     busy = 0
+    dumps = []
     for s, e, name in ev:
         busy += e - s
+        if x1_launch_kind(name) == "dump":
+            dumps.append((e - s) / 1e3)
         print(f"{(s - t0) / 1e3:9.1f} us {(e - s) / 1e3:8.1f} us  {name[:100]}")
     print(f"span {(ev[-1][1] - t0) / 1e3:.1f} us, kernels {len(ev)}, busy {busy / 1e3:.1f} us")
+    if dumps:
+        # segments of dump launches end after launches 1, 3, 7, 15, .. and the last
+        segs, a = [], 0
+        while a < len(dumps):
+            b = min(len(dumps), 2 * a + 1)
+            segs.append(round(sum(dumps[a:b]) / (b - a), 1))
+            a = b
+        print(f"dump launches {len(dumps)}, {sum(dumps) / 1e3:.2f} ms, mean per segment (us): {segs}")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--report")
+    ap.add_argument("--last-search", action="store_true",
+                    help="with --report: the last search of a bench.py trace")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--b", type=int, default=1024)
     ap.add_argument("--k", type=int, default=10)
@@ -43,7 +77,7 @@ def main():
     ap.add_argument("--warm", type=int, default=3)
     a = ap.parse_args()
     if a.report:
-        report(a.report)
+        report(a.report, last_search=a.last_search)
         return
     import torch
     from vsearch import faiss as vf
