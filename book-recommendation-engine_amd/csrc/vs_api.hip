@@ -903,6 +903,15 @@ static bool dump_enabled() {
   return v;
 }
 
+// The MFMA shape of the int8 inner-product dump launches (vs_gemm_x1.hip,
+// x1_has_s16): 16x16x64 by default; env VS_X1_DUMP_MFMA=32 runs them on the
+// 32x32x32 form (A/B and the equality tests; read once per search, beside the
+// dump switch — never per launch).  Both forms leave the same lists.
+static bool dump_mfma32() {
+  const char* e = getenv("VS_X1_DUMP_MFMA");
+  return e && atoi(e) == 32;
+}
+
 // Query cuts taken again after every replay of a cutting pass (default; env
 // VS_X1_RECUT=0 sets them once, after the list launch; 2 refreshes them with
 // the separate replay and cut kernels instead of the fused one; A/B, read at
@@ -1181,6 +1190,7 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
         x.qbkey = bk;
         x.qcut_m = need;
         x.dump = true;
+        x.dump32 = dump_mfma32();
         x.recut = recut_mode();
         x.dcount = dc;
         x.dslot = ds;

@@ -43,6 +43,16 @@
 //    segments of launches) admits the dumped rows into the lists exactly as a
 //    list launch would have — same keys, same order, same admission rule — so
 //    both kinds leave the same lists.
+// The int8 inner-product dump launches (the augmented L2 among them) run on
+// v_mfma_i32_16x16x64_i8 instead (template flag S16, the default; env
+// VS_X1_DUMP_MFMA=32 keeps the 32x32x32 form): 8 x 4 accumulators of 16 rows
+// x 16 queries per wave, one MFMA each per step — the same tile, cycles,
+// accumulator and fragment registers, LDS images and DMA pieces; the chip
+// holds a higher clock on that shape (tools/mfma_ceiling.hip: 1.14x by wall
+// with no loads).  Lane l then holds query l & 15 of four 16-query blocks, and
+// lanes l and l ^ 32 feed the same lane list: the dump epilogue exchanges
+// their candidate counts so that the lists, slots and dump order are exactly
+// the 32x32 form's (epilogue16 below).
 // The lists are per lane, so a list launch pays for a wave's rows whenever ANY
 // of its 64 lanes admits one (an exec-masked insertion chain per block that
 // passes somewhere): about a sixth of the int8 pass (profiles/r04a/x1_probes.txt:
@@ -126,6 +136,16 @@ constexpr int x1_sched(int el, bool dump, bool hyb = false) {
 // cosine keys also need the row norms in the kernel.
 constexpr bool x1_has_dump(int mode, int el) {
   return mode == MODE_IP || (mode == MODE_COS && el == FILTER_I8);
+}
+// The dump launches on v_mfma_i32_16x16x64_i8 (template flag S16; default):
+// int8 inner-product passes (the augmented L2 among them) under the segmented
+// schedule.  The same cycles per step as the 32x32x32 form, but the chip holds
+// a higher clock on the 16x16 shape (tools/mfma_ceiling.hip).
+// List and hybrid launches, the cosine and every bf16 kernel stay on 32x32
+// (the two bf16 shapes add their fp32 partial sums in different orders, so a
+// list launch and a dump launch would not give a row the same key bits).
+constexpr bool x1_has_s16(int mode, int el) {
+  return mode == MODE_IP && el == FILTER_I8 && x1_sched(el, true) == 2;
 }
 // The int8 cosine's dump form (its folded factors s_x / |x| take the place of
 // s_x; key and bound as in its list launches) is used only with VS_X1_COSDUMP=1
@@ -276,7 +296,7 @@ __device__ __forceinline__ float x1_key(int sum_bits, float qsc, float fx) {
 // slices (QG x 16 KB per step) and serves a database tile to QG workgroups;
 // slot / QG orders the splits, so with two rounds of workgroups per CU each
 // round covers its own DG / 2 splits.  Other grids: a plain dealing.
-template <int KR, int MODE, bool DUMP, int EL, bool HYB = false>
+template <int KR, int MODE, bool DUMP, int EL, bool HYB = false, bool S16 = false>
 __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     const char* __restrict__ XH, const float* __restrict__ xs, const float* __restrict__ xaux,
     const char* __restrict__ QH, const float* __restrict__ qs, const float* __restrict__ qaux,
@@ -287,6 +307,9 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     int* __restrict__ dcount, int* __restrict__ dslot, int dR, int qskip) {
   static_assert(!DUMP || x1_has_dump(MODE, EL), "dump form");
   static_assert(!HYB || (!DUMP && x1_has_dump(MODE, EL)), "hybrid launch");
+  static_assert(!S16 || (DUMP && !HYB && x1_has_s16(MODE, EL)), "16x16x64 form");
+  // query blocks per lane: two of 32 queries, or (S16) four of 16
+  constexpr int NQB = S16 ? 4 : 2;
   constexpr int NBUF = kNbuf;
   constexpr int kStepB = kT * 64;  // one operand tile of one 32-element step: 16 KB
   constexpr int D = NBUF - 1;      // steps in flight
@@ -345,11 +368,11 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   // next n: ~24 dumps per list, within the slots)
   const int tsw = HYB ? t0 + (t1 - t0 + 3) / 4 : t1;
 
-  int gq[2], selfrow[2];
-  float qa[2], qsc[2];
+  int gq[NQB], selfrow[NQB];
+  float qa[NQB], qsc[NQB];
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    gq[qb] = qt * kT + 64 * wq + 32 * qb + c32;
+  for (int qb = 0; qb < NQB; ++qb) {
+    gq[qb] = qt * kT + 64 * wq + (S16 ? 16 * qb + (lane & 15) : 32 * qb + c32);
     qa[qb] = 0.0f;
     if constexpr (MODE == MODE_L2 || (MODE == MODE_COS && EL != FILTER_I8))
       qa[qb] = gq[qb] < nqa ? qaux[gq[qb]] : 0.0f;
@@ -358,7 +381,8 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     selfrow[qb] = qrow ? (gq[qb] < nqa ? qrow[gq[qb]] : -1) : self0 >= 0 ? (int)(self0 + gq[qb]) : -1;
   }
   const int P = nsplit * 4;
-  const int pl = sp * 4 + wr * 2 + h;
+  // (S16: the list of a row is still bit 2 of its slot, here bit 4 of the lane)
+  const int pl = sp * 4 + wr * 2 + (S16 ? (lane >> 4) & 1 : h);
   // List launches: the lane's sorted lists (admission limit: the last entry).
   // Dump launches: the query's cut (padding queries: nothing passes) and the
   // lane list's running dump count over the search's launches.
@@ -368,10 +392,10 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   constexpr int KL = KR;
   float lk[2][KL];
   int li[2][KL];
-  float tq[2] = {0.0f, 0.0f};
-  int dc[2] = {0, 0};
+  float tq[NQB] = {};
+  int dc[NQB] = {};
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
+  for (int qb = 0; qb < NQB; ++qb) {
     if constexpr (DUMP) {
       // the cut, or the list's own last entry after the first launch when
       // that is lower (a row at or above it can never enter this list: its
@@ -458,11 +482,11 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     // with a negative sum scores highest with its smallest factor, so it can
     // clear the limit only if fl(sum * fl(s_q * fmin)) does (rows with sums
     // >= 0 always clear it, and the threshold is below 0).
-    int Tq[2] = {0, 0};
+    int Tq[NQB] = {};
     float fm = 0.0f, fn = FLT_MAX;  // the dump tiles' largest and smallest row factors
     auto set_Tq = [&]() {
 #pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
+      for (int qb = 0; qb < NQB; ++qb) {
         const float c = qsc[qb] * fm, cn = qsc[qb] * fn, last = tq[qb];
         Tq[qb] = (c > 0.0f && -last >= 0.0f)                    ? i8_threshold(-last, c)
                  : (cn > 0.0f && cn <= FLT_MAX && -last < 0.0f) ? min(i8_threshold(-last, cn), -1)
@@ -552,6 +576,55 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       const AccT<EL> z = {};
       acc[rb][0] = mfma_blk<EL>(fa[rb], fb[0], z);
       acc[rb][1] = mfma_blk<EL>(fa[rb], fb[1], z);
+    };
+    // The 16x16x64 form (S16): 8 x 4 accumulators of 16 rows x 16 queries, one
+    // MFMA each per step (a 16x16x64 MFMA covers the whole 64-B step), the same
+    // 128 accumulator registers and the same 12 fragment registers (fa0 | fa1
+    // hold the 8 database fragments, fb0 | fb1 the 4 query fragments).  Lane l
+    // holds query l & 15 of each 16-query block and rows 16 b + 4 (l >> 4) + e
+    // (e = 0..3) of the wave's 128; as an operand it supplies row (or query)
+    // l & 15 and K group l >> 4.  Both operands take data chunk pi(g) for K
+    // group g, pi = (0, 3, 1, 2): a product is a sum over K, so any fixed
+    // permutation serves, and this one makes the 16-row reads of the unchanged
+    // images (chunk c of row r at c ^ ((r >> 2) & 3)) conflict-free — the
+    // identity would put lanes 0-3 and 20-23 of a ds_read_b128 lane group on
+    // the same banks (tests/test_x1_shape_model.py).
+    i32x4 acc16[S16 ? 8 : 1][4];
+    auto rd16 = [&](int buf) {
+      const char* base = smem + buf * 2 * kStepB;
+      const int c16 = lane & 15;
+      const int co = (((0x9C >> (2 * (lane >> 4))) & 3) ^ ((c16 >> 2) & 3)) * 16;
+      const char* cX = base + (128 * wr + c16) * 64 + co;
+      const char* cQ = base + kStepB + (64 * wq + c16) * 64 + co;
+      if constexpr (!VS_X1_P(2)) {
+        fb0[0] = *(const uint4*)cQ;
+        fb0[1] = *(const uint4*)(cQ + 16 * 64);
+        fb1[0] = *(const uint4*)(cQ + 32 * 64);
+        fb1[1] = *(const uint4*)(cQ + 48 * 64);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          fa0[b] = *(const uint4*)(cX + b * 16 * 64);
+          fa1[b] = *(const uint4*)(cX + (b + 4) * 16 * 64);
+        }
+      } else {
+        auto opq = [](uint4& u) { asm volatile("" : "+v"(u.x), "+v"(u.y), "+v"(u.z), "+v"(u.w)); };
+        asm volatile("" ::"v"(cX), "v"(cQ));
+        opq(fb0[0]), opq(fb0[1]), opq(fb1[0]), opq(fb1[1]);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) opq(fa0[b]), opq(fa1[b]);
+      }
+    };
+    // the four MFMAs of 16-row block b (C = 0 on a tile's first step)
+    auto mfma16_b = [&](int b, auto first_tag) {
+      if constexpr (S16) {
+        const uint4& a = b < 4 ? fa0[b & 3] : fa1[b & 3];
+#pragma unroll
+        for (int qb = 0; qb < 4; ++qb) {
+          const uint4& q = qb < 2 ? fb0[qb & 1] : fb1[qb & 1];
+          const i32x4 c = decltype(first_tag)::value ? i32x4{} : acc16[b][qb];
+          acc16[b][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(as_i4(a), as_i4(q), c, 0, 0, 0);
+        }
+      }
     };
     // the four LDS-DMA pieces of the load cursor's step, one at a time
     auto stage_piece = [&](int i) {
@@ -892,6 +965,81 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       }
     };
 
+    // The dump epilogue of the 16x16x64 form: the same lists, slots, counts and
+    // dump order as the 32x32 form's.  Slot 128 wr + 16 b + 4 g + e (g = lane >>
+    // 4) holds row t kT + (slot ^ f); a row's list is bit 2 of its slot, g & 1,
+    // so lanes l and l ^ 32 feed the SAME list of the same query and hold the
+    // same floor, threshold and running count.  Within a list the 32x32 form
+    // stores by ascending slot (32-row block, then jj, then e); here that is
+    // 16-row block b, then the lane below 32, then its partner, then e: per
+    // block the pair exchange their candidate counts (rows that take a slot
+    // only), the lower lane stores first and both advance the count by the sum.
+    // The control flow around the exchange is wave-uniform.
+    auto epilogue16 = [&](int t) {
+      if constexpr (S16) {
+        const bool plain = self0 < 0 && !qrow && (t + 1) * kT <= ntotal;
+        const int f = tile_perm(t);
+        const int fl = (4 * (lane >> 4)) ^ (f & 0x0C);
+        // uniform part (wr, b) + lane part (g); f leaves the low two bits (e)
+        auto rowof16 = [&](int b) { return t * kT + ((128 * wr + 16 * b) ^ (f & 0xF0)) + fl; };
+        // one bit per query block: all 32 rows of the lane feed one list under
+        // one threshold, so the test is one maximum and one compare per block
+        uint32_t pass = 0;
+#if VS_X1_STAMP
+        eA = stamp_now();
+#endif
+#pragma unroll
+        for (int qb = 0; qb < 4; ++qb) {
+          int amax = acc16[0][qb][0];
+#pragma unroll
+          for (int r = 1; r < 32; ++r) amax = max(amax, acc16[r >> 2][qb][r & 3]);
+          pass |= (uint32_t)(amax > Tq[qb]) << qb;
+        }
+        VS_X1_EMARK(6);
+        if constexpr (VS_X1_P(128)) {
+          asm volatile("" ::"v"(pass));
+          pass = 0;
+        }
+        if (__ballot(pass != 0) != 0) {  // uniform: rare
+          const int64_t nl = (int64_t)nqt * kT * P;
+#pragma unroll
+          for (int qb = 0; qb < 4; ++qb) {
+            if (__ballot((pass >> qb) & 1u) == 0) continue;  // uniform
+            int* const dst = dslot + ((int64_t)gq[qb] * P + pl) * 2;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+              uint32_t cm = 0;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) cm |= (uint32_t)(acc16[b][qb][e] > Tq[qb]) << e;
+              const int row0 = rowof16(b);
+              // rows past the corpus (the last tile's zero padding, whose sums
+              // of 0 clear a floor above 0) and the query's own row take no slot
+              // and are not counted
+              if (!plain) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  if (!(row0 + e < ntotal && row0 + e != selfrow[qb])) cm &= ~(1u << e);
+              }
+              if (__ballot(cm != 0) == 0) continue;  // uniform
+              const int n = __popc(cm);
+              const int np = __shfl_xor(n, 32);  // the partner's count (every lane active)
+              int c = dc[qb] + (lane >= 32 ? np : 0);
+              dc[qb] += n + np;  // counts on past dR (the replay fails the query)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                if (cm & (1u << e)) {
+                  // slot-major, as in the 32x32 form
+                  if (c < dR) *(i32x2*)(dst + (int64_t)c * nl * 2) = i32x2{row0 + e, acc16[b][qb][e]};
+                  ++c;
+                }
+              }
+            }
+          }
+        }
+        VS_X1_EMARK(8);
+      }
+    };
+
     constexpr int kSched = x1_sched(EL, DUMP, HYB);
     if constexpr (kSched == 1) {
 
@@ -1050,8 +1198,12 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     auto seg_step = [&](auto first_tag) {
       constexpr bool first = decltype(first_tag)::value;
       __builtin_amdgcn_sched_barrier(0);
-      rd(buf, 0, fa0, fb0);
-      rd(buf, 1, fa1, fb1);
+      if constexpr (S16) {
+        rd16(buf);
+      } else {
+        rd(buf, 0, fa0, fb0);
+        rd(buf, 1, fa1, fb1);
+      }
       __builtin_amdgcn_sched_barrier(0);
 #if !VS_X1_SEGDMA
       stage_step();
@@ -1071,15 +1223,20 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       __builtin_amdgcn_sched_barrier(0);
       VS_X1_MARK(2);
 #if !VS_X1_SEGDMA
-      if constexpr (first) {
+      if constexpr (S16) {
 #pragma unroll
-        for (int rb = 0; rb < 4; ++rb) mfma_rb_first(rb, fa0, fb0);
+        for (int b = 0; b < 8; ++b) mfma16_b(b, first_tag);
       } else {
+        if constexpr (first) {
 #pragma unroll
-        for (int rb = 0; rb < 4; ++rb) mfma_rb(rb, fa0, fb0);
+          for (int rb = 0; rb < 4; ++rb) mfma_rb_first(rb, fa0, fb0);
+        } else {
+#pragma unroll
+          for (int rb = 0; rb < 4; ++rb) mfma_rb(rb, fa0, fb0);
+        }
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb) mfma_rb(rb, fa1, fb1);
       }
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) mfma_rb(rb, fa1, fb1);
 #else
       {
         // step s+3's pieces into the image of step s-2 (read two barriers ago
@@ -1100,7 +1257,10 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
               : "memory");
         };
         static_assert(kStepB == 0x4000, "piece offsets");
-        if constexpr (first) {
+        if constexpr (S16) {
+          mfma16_b(0, first_tag);
+          mfma16_b(1, first_tag);
+        } else if constexpr (first) {
           mfma_rb_first(0, fa0, fb0);
           mfma_rb_first(1, fa0, fb0);
         } else {
@@ -1110,7 +1270,10 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         __builtin_amdgcn_sched_barrier(0);
         piece(0, lx, xl0, xstep);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (first) {
+        if constexpr (S16) {
+          mfma16_b(2, first_tag);
+          mfma16_b(3, first_tag);
+        } else if constexpr (first) {
           mfma_rb_first(2, fa0, fb0);
           mfma_rb_first(3, fa0, fb0);
         } else {
@@ -1120,13 +1283,23 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         __builtin_amdgcn_sched_barrier(0);
         piece(1, lx + 0x4000u, soff, qstep);
         __builtin_amdgcn_sched_barrier(0);
-        mfma_rb(0, fa1, fb1);
-        mfma_rb(1, fa1, fb1);
+        if constexpr (S16) {
+          mfma16_b(4, first_tag);
+          mfma16_b(5, first_tag);
+        } else {
+          mfma_rb(0, fa1, fb1);
+          mfma_rb(1, fa1, fb1);
+        }
         __builtin_amdgcn_sched_barrier(0);
         piece(2, lx + 0x400u, xl2, xstep);
         __builtin_amdgcn_sched_barrier(0);
-        mfma_rb(2, fa1, fb1);
-        mfma_rb(3, fa1, fb1);
+        if constexpr (S16) {
+          mfma16_b(6, first_tag);
+          mfma16_b(7, first_tag);
+        } else {
+          mfma_rb(2, fa1, fb1);
+          mfma_rb(3, fa1, fb1);
+        }
         __builtin_amdgcn_sched_barrier(0);
         piece(3, lx + 0x4400u, soff + 1024u, qstep);
         __builtin_amdgcn_sched_barrier(0);
@@ -1147,7 +1320,13 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         for (int k = 1; k < nksteps; ++k) seg_step(std::false_type{});
         // the tile's epilogue, beside the partner's matrix segment
         if constexpr (!VS_X1_P(8)) {
-          epilogue(t, dm_tag);
+          if constexpr (S16) epilogue16(t);
+          else epilogue(t, dm_tag);
+        } else if constexpr (S16) {
+#pragma unroll
+          for (int b = 0; b < 8; ++b)
+#pragma unroll
+            for (int qb = 0; qb < 4; ++qb) asm volatile("" ::"v"(acc16[b][qb]));
         } else {
 #pragma unroll
           for (int rb = 0; rb < 4; ++rb)
@@ -1186,13 +1365,17 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   // the list offsets are recomputed from the lane id here (not kept live
   // across the main loop: registers)
   const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  const int pl0 = sp * 4 + wr * 2 + (ln >> 5);
+  const int pl0 = sp * 4 + wr * 2 + (S16 ? (ln >> 4) & 1 : ln >> 5);
   // (a hybrid launch stored its lists at the switch, which every workgroup
   // with a tile reaches: its lists are dead past it, registers)
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int64_t g = (int64_t)(qt * kT + 64 * wq + 32 * qb + (ln & 31)) * P + pl0;
-    if (DUMP || (HYB && t1 > t0)) {
+  for (int qb = 0; qb < NQB; ++qb) {
+    const int64_t g =
+        (int64_t)(qt * kT + 64 * wq + (S16 ? 16 * qb + (ln & 15) : 32 * qb + (ln & 31))) * P + pl0;
+    if constexpr (S16) {
+      // lanes l and l ^ 32 hold the same count of the same list: one writes it
+      if (ln < 32) dcount[g] = dc[qb];
+    } else if (DUMP || (HYB && t1 > t0)) {
       dcount[g] = dc[qb];
     } else if (HYB) {  // no tile: empty lists
       const int64_t o = g * KP;
@@ -1447,7 +1630,15 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
     // launches dump is timed apart ("<name>_list")
     if (a.timing)
       a.timing->begin(st, !(later_dump && nlaunch > 1) || c > 0, (double)(p1 - p0) / nparts);
-    if (later_dump && c > 0) {
+    if (later_dump && c > 0 && x1_has_s16(MODE, EL) && !a.dump32) {
+      if constexpr (x1_has_s16(MODE, EL))
+        hipLaunchKernelGGL((gemm_topk_x1<KR, MODE, true, EL, false, true>), dim3(nqt * a.nsplit),
+                           dim3(512), 0, st, (const char*)a.XH, a.xs, a.xaux, (const char*)a.QH,
+                           a.qs, a.qaux, a.nqa, (int)(ldb / 64), a.ntotal, ntiles, a.nsplit, nqt,
+                           a.qtile0, a.self0, a.qrow, a.qcount, p0, p1, nparts, part.KP, qg,
+                           part.key, part.id, a.xgmax, a.xgmin, a.qcut, a.dcount, a.dslot, a.dR,
+                           a.qskip);
+    } else if (later_dump && c > 0) {
       if constexpr (x1_has_dump(MODE, EL))
         hipLaunchKernelGGL((gemm_topk_x1<KR, MODE, true, EL>), dim3(nqt * a.nsplit), dim3(512), 0,
                            st, (const char*)a.XH, a.xs, a.xaux, (const char*)a.QH, a.qs, a.qaux,

@@ -97,7 +97,8 @@ hipError_t launch_skinny_topk(int KP, int mode, int nq, const void* X, int esize
 // product per fp32 product over a low-precision "filter plane" of rows and
 // queries: bf16 (RNE) on v_mfma_f32_32x32x16_bf16, or int8 with one fp32 scale
 // per row (code = rint(x / s), s = max|x| / 127) on v_mfma_i32_32x32x32_i8
-// (twice the bf16 rate, exact int32 sums, half the bytes per element).
+// (twice the bf16 rate, exact int32 sums, half the bytes per element; the
+// inner-product dump launches on v_mfma_i32_16x16x64_i8, the same sums).
 enum Filter : int { FILTER_BF16 = 0, FILTER_I8 = 1 };
 inline int filter_bytes(int filter) { return filter == FILTER_I8 ? 1 : 2; }
 // Filter planes are stored TILE-MAJOR: [tile of 256 rows][64-B step][256
@@ -130,6 +131,7 @@ struct X1Args {
   // Dump launches (vs_gemm_x1.hip header): after the pass's first launch the
   // cuts are set and the later launches store the blocks below them
   bool dump = false;
+  bool dump32 = false;           // int8 dump launches on the 32x32x32 MFMA form (A/B; default 16x16x64)
   float* qcut = nullptr;         // per query (nqa): the cut, set after the first launch
   const double* qbkey = nullptr; // per query: the verification's bound B (x1_qcut)
   int qcut_m = 0;                // the M of the verification
