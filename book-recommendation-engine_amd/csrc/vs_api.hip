@@ -922,6 +922,14 @@ static int recut_mode() {
   return v == 0 ? 0 : v == 2 ? 2 : 1;
 }
 
+// Exact-key cuts of the int8 inner-product pass over fp32 rows (default; env
+// VS_X1_ECUT=0 keeps a_M + 2B alone, for A/B; read once per search, beside the
+// dump switch)
+static bool ecut_enabled() {
+  const char* e = getenv("VS_X1_ECUT");
+  return !e || atoi(e) != 0;
+}
+
 // Small batches through the staged engine's skinny passes (env
 // VS_SMALL_FILTER=0 keeps the exact streaming kernels, for A/B; read at every
 // search), over indexes of at least kSmallFilterMinRows rows.
@@ -1192,6 +1200,23 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
         x.dump = true;
         x.dump32 = dump_mfma32();
         x.recut = recut_mode();
+        // exact-key cuts: the int8 inner-product pass of an fp32 index (the
+        // augmented L2 and bf16-plane passes keep a_M + 2B)
+        if (i8 && mode == MODE_IP && idx->esize == 4 && need <= kEcutMaxM && ecut_enabled()) {
+          int* ci = nullptr;
+          VS_HIP(scr.alloc((void**)&x.qam, (size_t)qa_rows * sizeof(float)), "vs: scratch");
+          VS_HIP(scr.alloc((void**)&x.ecut_key, (size_t)qa_rows * kEcutMaxM * sizeof(float)),
+                 "vs: scratch");
+          VS_HIP(scr.alloc((void**)&ci, (size_t)qa_rows * kEcutMaxM * sizeof(int)), "vs: scratch");
+          VS_HIP(hipMemsetD32Async((hipDeviceptr_t)x.qam, 0x7f7fffff, (size_t)qa_rows, st),
+                 "vs: cuts");
+          VS_HIP(hipMemsetAsync(ci, 0xFF, (size_t)qa_rows * kEcutMaxM * sizeof(int), st),
+                 "vs: cuts");
+          x.ecut_id = ci;
+          x.ecut_x = (const float*)idx->codes;
+          x.ecut_q = Q;
+          x.ecut_ld = idx->ld;
+        }
         x.dcount = dc;
         x.dslot = ds;
         x.dR = dR;

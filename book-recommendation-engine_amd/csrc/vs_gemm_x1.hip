@@ -1488,6 +1488,7 @@ static int x1_qg() {
 
 static hipError_t launch_qcut(const X1Args& a, Partials part, hipStream_t st);
 static hipError_t launch_x1_replay_cut(const X1Args& a, Partials part, hipStream_t st);
+static hipError_t launch_x1_ecut(const X1Args& a, Partials part, hipStream_t st);
 
 // XCD rounds of query-tile groups for grids of more than 8 groups (env
 // VS_X1_XCDG=0 turns them off, for A/B; read at every search)
@@ -1560,9 +1561,12 @@ constexpr int kSplitMinTiles = 16;
 // pass -1 %, profiles/r05u)
 // VS_X1_QUARTER=<F>: the list launch covers 1/F of the first chunk (0: off,
 // 1: 1/4 as F = 4)
-static int x1_first_den(int el) {
+// (round 9: the int8 pass too when its cuts are exact-key cuts — the looser
+// first cut then costs far fewer rows than the shorter list launch saves,
+// profiles/r09ec)
+static int x1_first_den(int el, bool ecut) {
   const char* e = getenv("VS_X1_QUARTER");
-  if (!e) return el == FILTER_BF16 ? 4 : 0;
+  if (!e) return el == FILTER_BF16 || ecut ? 4 : 0;
   const int v = atoi(e);
   return v == 1 ? 4 : v >= 2 ? v : 0;
 }
@@ -1600,14 +1604,16 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
   const bool hyb = dump && !split && x1_hybrid_on() && tiles0 >= kHybMinTiles;
   const bool later_dump = cutting || hyb;  // launches c > 0 are dump launches
   // the launches as part ranges [p0, p1) of nparts
-  // Quarter-chunk list launches (env VS_X1_QUARTER=0/1; default: bf16 passes): a
+  // Quarter-chunk list launches (env VS_X1_QUARTER=0/1/F; default: bf16 passes
+  // and int8 passes with exact-key cuts): a
   // cutting pass of nchunk launches lists only parts [0, 1) of 4 nchunk, then a
   // dump launch over [1, 4) and one launch per chunk.  The list launch runs at
   // ~2/3 of a dump launch's rate (a k = 60 pass of 5 chunks spent 15 of its
   // 58 ms in it, profiles/r05t), but cuts set from a quarter of the rows are
   // looser: C3 dumps 1.7x the rows, 76.5k vs 77.4k queries/s; k = 60 equal,
   // clustered +1.4 % (profiles/r05u).
-  const int F = x1_first_den(EL);
+  const bool ecut = MODE == MODE_IP && EL == FILTER_I8 && a.ecut_x && a.qam;
+  const int F = x1_first_den(EL, ecut);
   const bool quarter = cutting && !split && nchunk >= 4 && F >= 2 && per_block / (F * nchunk) >= 2;
   const bool sseg = split && x1_split_segments(den);
   int lg = 0;
@@ -1668,6 +1674,7 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
     }
     if (cutting && c == 0) {
       e = launch_qcut(a, part, st);
+      if (e == hipSuccess && ecut) e = launch_x1_ecut(a, part, st);
       if (e != hipSuccess) return e;
     }
     // Segments of dump launches end where the data seen doubles (after
@@ -1687,8 +1694,9 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
     // After the last replay nothing reads a new cut but the verification,
     // which takes a_M + 2B itself.
     if (later_dump && c > 0 && (sseg || ((c + 1) & c) == 0 || c + 1 == nlaunch)) {
-      e = cutting && a.recut && c + 1 < nlaunch ? launch_x1_replay_cut(a, part, st)
-                                                : launch_x1_replay(a, part, st);
+      const bool again = cutting && a.recut && c + 1 < nlaunch;
+      e = again ? launch_x1_replay_cut(a, part, st) : launch_x1_replay(a, part, st);
+      if (e == hipSuccess && again && ecut) e = launch_x1_ecut(a, part, st);
       if (e != hipSuccess) return e;
     }
   }
@@ -3050,6 +3058,10 @@ hipError_t launch_verify_wide(int mode, int nq_max, const int* qlist, const int*
 // entries gets none, and every value it ever held is >= the final a_M + 2B, so
 // the final cut is a floor for every row any launch dropped
 // (tests/test_cut_refresh_argument.py).
+// The int8 inner-product pass of an fp32 index lowers every cut further, to
+// e_M + 1.000001 B with e_M from exact keys ("Exact-key cuts", x1_ecut_kernel
+// below): such a cut may be below the final a_M + 2B, and what keeps it valid is
+// that no row it drops can be in the exact top M.
 
 // bkey[q]: the bound B of query q (bound_key over its split norms, the same
 // double the verification computes).
@@ -3346,7 +3358,7 @@ hipError_t launch_select_heads(Partials part, int nq, int KF, float* Dk, int64_t
 constexpr int kQcutThreads = 256;
 __global__ __launch_bounds__(kQcutThreads) void qcut_kernel(
     const float* __restrict__ lkey, const int* __restrict__ lid, int P, int LKP, int L, int M,
-    const double* __restrict__ bkey, int nq, float* __restrict__ cut) {
+    const double* __restrict__ bkey, int nq, float* __restrict__ cut, float* __restrict__ qam) {
   const int q = blockIdx.x;
   const int tid = threadIdx.x;
   if (q >= nq) return;  // uniform over the workgroup
@@ -3389,6 +3401,7 @@ __global__ __launch_bounds__(kQcutThreads) void qcut_kernel(
   for (int b = 31; b >= 0; --b)
     if (count_below(x + (1ull << b)) < M) x += 1ull << b;
   const float aM = key_unorder((uint32_t)x);
+  if (tid == 0 && qam) qam[q] = aM;  // x1_ecut_kernel's candidates: the entries <= a_M
   const double tp = (double)aM + 2.000001 * bkey[q];
   if (tid == 0 && isfinite(tp) && tp < (double)FLT_MAX) {
     float t = (float)tp;
@@ -3423,7 +3436,7 @@ __global__ __launch_bounds__(256) void x1_replay_cut_kernel(
     int* __restrict__ pid, int P, int KP, const float* __restrict__ qs,
     const float* __restrict__ xs, int64_t self0, int ntotal, int dR, int64_t nl,
     float* __restrict__ qcut, unsigned long long* __restrict__ stats, int M,
-    const double* __restrict__ bkey) {
+    const double* __restrict__ bkey, float* __restrict__ qam) {
   __shared__ int hist[256];
   __shared__ int wsum[4];
   __shared__ int s_over, sel_digit, sel_before;
@@ -3563,6 +3576,7 @@ __global__ __launch_bounds__(256) void x1_replay_cut_kernel(
   }
   if (tid == 0) {
     const float aM = key_unorder(pre);
+    if (qam) qam[q] = aM;
     const double tp = (double)aM + 2.000001 * bkey[q];
     if (isfinite(tp) && tp < (double)FLT_MAX) {
       float t = (float)tp;
@@ -3573,6 +3587,175 @@ __global__ __launch_bounds__(256) void x1_replay_cut_kernel(
 }
 
 constexpr int kReplayCutMaxP = 256;
+
+// Exact-key cuts (int8 inner-product passes over fp32 rows; X1Args::ecut_x).
+// Let e_M be the M-th smallest EXACT key over any M (or more) distinct
+// admissible rows: the true M-th best key E_M is at most e_M.  A row whose
+// approximate key is >= e_M + 1.000001 B has an exact key >= e_M + 0.000001 B >
+// e_M >= E_M (|a - e| <= B): it is outside the exact top M, ties included, so
+// no check needs it — the window above the M-th key is B where a_M + 2B takes
+// 2B (a_M <= E_M + B is all the approximate keys can say).  The verification
+// already takes T = min(T, cut) and decides T - B > E_M itself, so a cut can
+// only hand a query on, never change an answer.
+//
+// After every cut kernel (x1_qcut or the fused replay + cut, which leave a_M in
+// qam[q]) one workgroup per query takes the query's list entries with key <=
+// a_M — the M best approximate ones and their ties, at most kEcutCand of them
+// in (list, position) order, the same set whichever kernel took a_M — adds the
+// rows kept from the earlier cuts (ecut_key / ecut_id: the M best exact keys
+// scored so far, so a refresh scores only rows it has not seen and e_M only
+// falls), scores the new rows with the verification's own arithmetic
+// (wave_dot / wave_dot2's fp64 sums, exact_key<MODE_IP>: bit-identical to
+// verify_rescore_kernel), ranks the union by (key, row) and writes
+// cut = min(cut, fl_up(e_M + 1.000001 B)).  -FLT_MAX stays, fewer than M rows
+// give no exact cut, and list entries are admissible rows already (inside the
+// corpus, not the query's own).
+constexpr int kEcutCand = 64;
+__global__ __launch_bounds__(256) void x1_ecut_kernel(
+    const float* __restrict__ lkey, const int* __restrict__ lid, int P, int LKP, int L, int M,
+    const double* __restrict__ bkey, const float* __restrict__ qam, const float* __restrict__ X,
+    const float* __restrict__ Q, int64_t ld, int ntotal, float* __restrict__ ckey,
+    int* __restrict__ cid, float* __restrict__ qcut) {
+  constexpr int kU = kEcutMaxM + kEcutCand;
+  __shared__ int cand[kEcutCand];
+  __shared__ float uk[kU];
+  __shared__ int ui[kU];
+  __shared__ int wsum[4];
+  __shared__ int un;
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float cut = qcut[q];
+  const float aM = qam[q];
+  // the rows kept from the earlier cuts and the query's slice, loaded beside the
+  // lists (one memory round trip for the three; the kernel is a chain of them)
+  float* ck = ckey + (int64_t)q * kEcutMaxM;
+  int* ci = cid + (int64_t)q * kEcutMaxM;
+  if (tid < kEcutMaxM) {
+    ui[tid] = ci[tid];  // valid entries first (written by rank below), -1 after them
+    uk[tid] = ck[tid];
+  }
+  const float* qrow = Q + (int64_t)q * ld;
+  const bool pairs = ld <= 256 * kQV;  // two rows per step, the query in registers
+  QSlice qsl;
+  if (pairs) load_qslice(qrow, ld, lane, qsl);
+  // uniform: a list out of slots, or no a_M yet (fewer than M entries)
+  if (cut == -FLT_MAX || !(aM < FLT_MAX)) return;
+  // the candidates: entries with key <= a_M, in (list, position) order
+  const bool vec = L == 8 && LKP % 4 == 0;  // lane lists as 16-B pieces
+  int ncand = 0;
+  for (int p0 = 0; p0 < P && ncand < kEcutCand; p0 += 256) {  // uniform
+    const int p = p0 + tid;
+    int ids[8];  // (static indices only: registers)
+    float lk[8];
+    int c = 0;
+    const int64_t o = ((int64_t)q * P + p) * LKP;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ids[e] = -1, lk[e] = FLT_MAX;
+    if (p < P && vec) {
+#pragma unroll
+      for (int e = 0; e < 8; e += 4) {
+        const f32x4 kv = *(const f32x4*)(lkey + o + e);
+        const int4 iv = *(const int4*)(lid + o + e);
+        lk[e] = kv.x, lk[e + 1] = kv.y, lk[e + 2] = kv.z, lk[e + 3] = kv.w;
+        ids[e] = iv.x, ids[e + 1] = iv.y, ids[e + 2] = iv.z, ids[e + 3] = iv.w;
+      }
+    } else if (p < P) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e < L) ids[e] = lid[o + e], lk[e] = lkey[o + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if (ids[e] >= 0 && ids[e] < ntotal && lk[e] <= aM)
+        ++c;
+      else
+        ids[e] = -1;
+    }
+    int inc = c;  // inclusive prefix over the workgroup's lists
+    for (int o2 = 1; o2 < 64; o2 <<= 1) {
+      const int t = __shfl_up(inc, o2);
+      if (lane >= o2) inc += t;
+    }
+    __syncthreads();  // the previous round's reads of wsum
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int before = ncand + inc - c;
+    for (int w = 0; w < wv; ++w) before += wsum[w];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (ids[e] >= 0) {
+        if (before < kEcutCand) cand[before] = ids[e];
+        ++before;
+      }
+    ncand += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  }
+  ncand = min(ncand, kEcutCand);
+  // the rows kept from the earlier cuts, then the candidates not among them
+  __syncthreads();  // cand, ui
+  int m0 = 0;
+  for (int t = 0; t < kEcutMaxM; ++t) m0 += ui[t] >= 0 ? 1 : 0;
+  if (tid == 0) un = m0;
+  __syncthreads();
+  if (tid < ncand) {
+    const int r = cand[tid];
+    bool found = false;
+    for (int t = 0; t < m0; ++t) found |= ui[t] == r;
+    if (!found) ui[atomicAdd(&un, 1)] = r;  // < m0 + ncand <= kU
+  }
+  __syncthreads();
+  const int n = un;
+  if (pairs) {
+    for (int j = m0 + 2 * wv; j < n; j += 8) {
+      const int ra = ui[j], rb = j + 1 < n ? ui[j + 1] : ra;
+      double da, db;
+      wave_dot2<false, float>(X + (int64_t)ra * ld, X + (int64_t)rb * ld, qsl, ld, lane, da, db);
+      if (lane == 0) {
+        uk[j] = exact_key<MODE_IP>((float)da, q, ra, nullptr, nullptr, nullptr, nullptr);
+        if (j + 1 < n)
+          uk[j + 1] = exact_key<MODE_IP>((float)db, q, rb, nullptr, nullptr, nullptr, nullptr);
+      }
+    }
+  } else {
+    for (int j = m0 + wv; j < n; j += 4) {
+      const int r = ui[j];
+      const double acc = wave_dot<false, float>(X + (int64_t)r * ld, qrow, ld, lane);
+      if (lane == 0) uk[j] = exact_key<MODE_IP>((float)acc, q, r, nullptr, nullptr, nullptr, nullptr);
+    }
+  }
+  __syncthreads();
+  // rank by (key, row) (distinct rows): the M best stay for the next cut
+  if (tid < n) {
+    const float k0 = uk[tid];
+    const int i0 = ui[tid];
+    int rank = 0;
+    for (int t = 0; t < n; ++t) rank += lex_less(uk[t], ui[t], k0, i0) ? 1 : 0;
+    if (rank < M) {
+      ck[rank] = k0;
+      ci[rank] = i0;
+    }
+    if (rank == M - 1) {  // e_M
+      const double tp = (double)k0 + 1.000001 * bkey[q];
+      if (isfinite(tp) && tp < (double)FLT_MAX) {
+        float t = (float)tp;
+        if ((double)t < tp) t = nextafterf(t, INFINITY);
+        if (t < cut) qcut[q] = t;
+      }
+    }
+  }
+  // (n < M: the ranks 0 .. n-1 hold the rows; the entries after them are -1
+  // already — the kept set only grows up to M)
+}
+
+static hipError_t launch_x1_ecut(const X1Args& a, Partials part, hipStream_t st) {
+  if (!a.ecut_x || !a.ecut_q || !a.qam || !a.ecut_key || !a.ecut_id || a.nqa <= 0)
+    return hipSuccess;
+  if (a.qcut_m < 1 || a.qcut_m > kEcutMaxM || a.ecut_ld % 4 != 0 || x1_lane_len() > 8)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(x1_ecut_kernel, dim3(a.nqa), dim3(256), 0, st, part.key, part.id, part.P,
+                     part.KP, x1_lane_len(), a.qcut_m, a.qbkey, a.qam, a.ecut_x, a.ecut_q,
+                     a.ecut_ld, a.ntotal, a.ecut_key, a.ecut_id, a.qcut);
+  return hipGetLastError();
+}
 
 hipError_t launch_qbound(int mode, const float* Q, int64_t ld, const float* qn, int filter,
                          const unsigned* stats, const float* qr2i8, int nq, double* bkey,
@@ -3597,7 +3780,7 @@ hipError_t launch_qbound(int mode, const float* Q, int64_t ld, const float* qn, 
 static hipError_t launch_qcut(const X1Args& a, Partials part, hipStream_t st) {
   const int nq = a.nqa;
   hipLaunchKernelGGL(qcut_kernel, dim3(nq), dim3(kQcutThreads), 0, st, part.key, part.id, part.P, part.KP,
-                     x1_lane_len(), a.qcut_m, a.qbkey, nq, a.qcut);
+                     x1_lane_len(), a.qcut_m, a.qbkey, nq, a.qcut, a.qam);
   return hipGetLastError();
 }
 
@@ -3616,11 +3799,11 @@ static hipError_t launch_x1_replay_cut(const X1Args& a, Partials part, hipStream
   if (a.filter == FILTER_I8)
     hipLaunchKernelGGL((x1_replay_cut_kernel<8, FILTER_I8>), dim3(a.nqa), block, 0, st, a.dcount,
                        a.dslot, part.key, part.id, part.P, part.KP, a.qs, a.xs, a.self0, a.ntotal,
-                       a.dR, nl, a.qcut, a.dstats, a.qcut_m, a.qbkey);
+                       a.dR, nl, a.qcut, a.dstats, a.qcut_m, a.qbkey, a.qam);
   else
     hipLaunchKernelGGL((x1_replay_cut_kernel<8, FILTER_BF16>), dim3(a.nqa), block, 0, st, a.dcount,
                        a.dslot, part.key, part.id, part.P, part.KP, a.qs, a.xs, a.self0, a.ntotal,
-                       a.dR, nl, a.qcut, a.dstats, a.qcut_m, a.qbkey);
+                       a.dR, nl, a.qcut, a.dstats, a.qcut_m, a.qbkey, a.qam);
   return hipGetLastError();
 }
 

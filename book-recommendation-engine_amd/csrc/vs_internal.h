@@ -136,6 +136,17 @@ struct X1Args {
   const double* qbkey = nullptr; // per query: the verification's bound B (x1_qcut)
   int qcut_m = 0;                // the M of the verification
   int recut = 1;                 // cuts after every replay: 0 set once, 1 fused, 2 replay + x1_qcut
+  // Exact-key cuts (vs_gemm_x1.hip "Exact-key cuts"; int8 inner-product passes
+  // over fp32 rows): every cut is also lowered to e_M + 1.000001 B.  ecut_x = the
+  // fp32 rows (null: a_M + 2B alone), ecut_q = the stage's fp32 queries, both of
+  // stride ecut_ld; qam / ecut_key / ecut_id = scratch (per query: the last
+  // a_M; the kEcutMaxM best exact keys scored so far and their rows)
+  const float* ecut_x = nullptr;
+  const float* ecut_q = nullptr;
+  int64_t ecut_ld = 0;
+  float* qam = nullptr;
+  float* ecut_key = nullptr;
+  int* ecut_id = nullptr;
   int* dcount = nullptr;         // [nq_pad][P] dumps per lane list (zeroed before the pass)
   int* dslot = nullptr;          // [nq_pad][P][dR][2] dumped (row, raw sum) pairs
   int dR = 0;                    // dump slots per lane list and segment
@@ -155,6 +166,7 @@ struct X1Args {
   const int* qcount = nullptr;   // gathered batch: device-side query count
 };
 constexpr int kX1Q = 256;  // queries (and database rows) per x1 tile
+constexpr int kEcutMaxM = 32;  // exact-key cuts: the largest M (inner product: k <= 16)
 // int8 sums stay exact in int32 up to this many elements per row.
 constexpr int64_t kI8MaxLd = 131072;
 // Candidates merged from the lane lists for `need` exact entries (24, 32, 64 or
