@@ -37,6 +37,9 @@ struct vs_index {
   int64_t ntotal = 0;
   int64_t capacity = 0;  // rows allocated (multiple of kRowPad, >= ntotal + 256)
   int64_t id_base = 0;
+  // bumped by whatever moves rows or changes labels (add, remove_ids, reset, a
+  // tombstone pack, set_id_base): a selector built before is stale
+  uint64_t gen = 0;
   char* codes = nullptr;   // [capacity][ld] elements
   int64_t rowbytes() const { return ld * esize; }
   char* row(int64_t r) const { return codes + r * rowbytes(); }
@@ -109,6 +112,22 @@ struct vs_index {
   std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
   hipStream_t wst = nullptr;  // the index's own (non-blocking) writer stream
 };
+
+// A selector of one index (vs_selector_create): the selected rows in place as
+// a bitmap and as an ascending list (vs_select.hip), valid while the index's
+// generation is the one it was built at.
+struct vs_selector {
+  vs_index* idx = nullptr;
+  int device = 0;
+  uint64_t gen = 0;
+  int64_t count = 0;         // selected live rows
+  uint32_t* rbits = nullptr;  // [whole compaction blocks over ntotal] row bitmap
+  int* list = nullptr;        // [count rounded up to kBN] ascending rows, padded
+};
+
+// Route (b) of vs_search_sel serves selections that leave at most this many
+// live rows out (a fixed condition of the route, not a tuned threshold).
+constexpr int64_t kSelMaxExcluded = 256;
 
 namespace {
 
@@ -2028,6 +2047,7 @@ int vs_add(vs_index* idx, const float* x, int64_t n, int flags, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   std::unique_lock<std::shared_mutex> lk(idx->mu);
   DeviceGuard g(idx->device);
+  ++idx->gen;
   int rc = make_room(idx, n, st);
   if (rc) return rc;
   const hipMemcpyKind kind = (flags & VS_IN_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -2072,6 +2092,7 @@ int vs_add_synthetic(vs_index* idx, int64_t n, uint64_t seed, int64_t row0, void
   hipStream_t st = (hipStream_t)stream;
   std::unique_lock<std::shared_mutex> lk(idx->mu);
   DeviceGuard g(idx->device);
+  ++idx->gen;
   int rc = make_room(idx, n, st);
   if (rc) return rc;
   VS_HIP(launch_fill_synthetic(idx->row(idx->ntotal), idx->esize, n, idx->d, idx->ld, seed, row0,
@@ -2097,6 +2118,7 @@ int vs_add_synthetic_ids(vs_index* idx, const int64_t* ids, int64_t n, uint64_t 
   hipStream_t st = (hipStream_t)stream;
   std::unique_lock<std::shared_mutex> lk(idx->mu);
   DeviceGuard g(idx->device);
+  ++idx->gen;
   int rc = make_room(idx, n, st);
   if (rc) return rc;
   Scratch scr(st);
@@ -2121,6 +2143,7 @@ int vs_reset(vs_index* idx) {
   std::unique_lock<std::shared_mutex> lk(idx->mu);
   DeviceGuard g(idx->device);
   VS_HIP(wait_readers(idx), "vs_reset");
+  ++idx->gen;
   free_storage(idx);
   for (int p = 0; p < 2; ++p)
     if (idx->bstats[p]) VS_HIP(hipMemset(idx->bstats[p], 0, 4 * sizeof(unsigned)), "vs_reset");
@@ -2186,6 +2209,7 @@ int vs_set_id_base(vs_index* idx, int64_t id_base) {
   if (!idx) return fail(VS_E_INVALID, "vs_set_id_base: null index");
   if (id_base < 0) return fail(VS_E_INVALID, "vs_set_id_base: negative base");
   std::unique_lock<std::shared_mutex> lk(idx->mu);
+  if (id_base != idx->id_base) ++idx->gen;
   idx->id_base = id_base;
   return VS_OK;
 }
@@ -2288,6 +2312,314 @@ int vs_search(vs_index* idx, const float* x, int64_t n, int64_t k, float* D, int
     VS_HIP(hipStreamSynchronize(st), "vs_search: synchronise");
   } else {
     VS_HIP(hipGetLastError(), "vs_search");
+  }
+  return VS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One chunk of a selector search (vs_search_sel; DESIGN.md "Selector searches").
+// `streaming`: the call has at most kSkinnyMaxQ queries (the streaming kernel
+// where its queries fit the LDS).
+int run_selected(vs_index* idx, const vs_selector* sel, const SearchArgs& a, bool streaming,
+                 hipStream_t st) {
+  const bool tie_rule = a.mode == MODE_IP && !a.raw;
+  const int64_t need = tie_rule ? 2 * (int64_t)a.k - 1 : a.k;
+  const int64_t excluded = idx->live() - sel->count;
+  if (excluded <= kSelMaxExcluded) {
+    // Route (b): the unselected engine in raw order for need + excluded
+    // entries (never more than the live rows), the unselected entries dropped
+    // stably, then faiss's tie rule over what is left.  The need + m
+    // lexicographically best rows minus m excluded ones hold the `need` best
+    // selected rows, and the rule is a function of those.
+    const int64_t k2 = std::min<int64_t>(need + excluded, idx->live());
+    if (k2 > INT_MAX / 2) return fail(VS_E_INVALID, "vs_search_sel: k too large");
+    Scratch scr(st);
+    float* D2 = nullptr;
+    int64_t* I2 = nullptr;
+    VS_HIP(scr.alloc((void**)&D2, (size_t)a.nq * k2 * sizeof(float)), "vs_search_sel: scratch");
+    VS_HIP(scr.alloc((void**)&I2, (size_t)a.nq * k2 * sizeof(int64_t)), "vs_search_sel: scratch");
+    SearchArgs b = a;
+    b.raw = 1;
+    b.k = (int)k2;
+    b.D = D2;
+    b.I = I2;
+    const int rc = run_topk(idx, b, st, VS_ENGINE_AUTO);
+    if (rc) return rc;
+    if (!tie_rule) {
+      VS_HIP(launch_sel_drop(a.mode, D2, I2, a.nq, (int)k2, sel->rbits, idx->id_base, a.D, a.I,
+                             a.k, st),
+             "vs_search_sel: drop launch");
+      return VS_OK;
+    }
+    const int kin = (int)std::min<int64_t>(need, sel->count);
+    float* D3 = nullptr;
+    int64_t* I3 = nullptr;
+    VS_HIP(scr.alloc((void**)&D3, (size_t)a.nq * kin * sizeof(float)), "vs_search_sel: scratch");
+    VS_HIP(scr.alloc((void**)&I3, (size_t)a.nq * kin * sizeof(int64_t)), "vs_search_sel: scratch");
+    VS_HIP(launch_sel_drop(a.mode, D2, I2, a.nq, (int)k2, sel->rbits, idx->id_base, D3, I3, kin,
+                           st),
+           "vs_search_sel: drop launch");
+    VS_HIP(launch_merge_parts(a.mode, D3, I3, 1, a.nq, kin, a.k, a.D, a.I, st),
+           "vs_search_sel: merge launch");
+    return VS_OK;
+  }
+  // Route (c): the gathered engine, one exact page.
+  if (need > VS_MAX_K)
+    return fail(VS_E_UNSUPPORTED,
+                "vs_search_sel: the gathered engine holds one exact page (inner product k <= 32, "
+                "L2 / raw order k <= 64); selections that leave at most 256 rows out take any k");
+  const int KP = kp_for(need);
+  const int count = (int)sel->count;
+  Scratch scr(st);
+  Partials part;
+  part.KP = KP;
+  const bool gemv_fits =
+      (size_t)kGemvMaxQ * idx->ld * sizeof(float) + 4 * kGemvMaxQ * 64 * 8 <= 64 * 1024;
+  if (streaming && gemv_fits) {
+    const int gmode = a.mode == MODE_L2 ? MODE_L2D : MODE_IP;
+    const int nblocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (count + 255) / 256));
+    part.P = nblocks;
+    const int nql = a.nq <= 2 ? a.nq : (a.nq <= 4 ? 4 : kGemvMaxQ);
+    const size_t n = (size_t)nql * part.P * KP;
+    VS_HIP(scr.alloc((void**)&part.key, n * sizeof(float)), "vs_search_sel: scratch");
+    VS_HIP(scr.alloc((void**)&part.id, n * sizeof(int)), "vs_search_sel: scratch");
+    for (int q0 = 0; q0 < a.nq; q0 += kGemvMaxQ) {
+      const int nc = std::min(kGemvMaxQ, a.nq - q0);
+      KernelTimer tm(st, "gemv_topk_rows");
+      VS_HIP(launch_gemv_topk_rows(KP, gmode, nc, idx->codes, idx->esize,
+                                   a.qbuf + (int64_t)q0 * idx->ld, idx->ld, sel->list, count,
+                                   nblocks, part, st),
+             "vs_search_sel: gemv_topk_rows launch");
+      tm.stop();
+      VS_HIP(launch_merge_partials(gmode, part, nc, a.k, idx->id_base, a.min_score,
+                                   a.D + (int64_t)q0 * a.k, a.I + (int64_t)q0 * a.k, a.k, st,
+                                   a.raw),
+             "vs_search_sel: merge launch");
+    }
+    return VS_OK;
+  }
+  const int nqt = a.nq_pad / kBQ;
+  const int ntiles = (count + kBN - 1) / kBN;
+  const int nsplit =
+      (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (512 + nqt - 1) / nqt));
+  part.P = 2 * nsplit;
+  const size_t n = (size_t)a.nq_pad * part.P * KP;
+  VS_HIP(scr.alloc((void**)&part.key, n * sizeof(float)), "vs_search_sel: scratch");
+  VS_HIP(scr.alloc((void**)&part.id, n * sizeof(int)), "vs_search_sel: scratch");
+  const void* qmat = a.qb16 ? a.qb16 : (const void*)a.qbuf;
+  {
+    KernelTimer tm(st, "gemm_topk_rows");
+    VS_HIP(launch_gemm_topk_rows(KP, a.mode, idx->codes, a.xaux, qmat, a.qaux, idx->ld,
+                                 idx->esize, sel->list, count, a.nq_pad, nsplit, part, st),
+           "vs_search_sel: gemm_topk_rows launch");
+    tm.stop();
+  }
+  VS_HIP(launch_merge_partials(a.mode, part, a.nq, a.k, idx->id_base, a.min_score, a.D, a.I, a.k,
+                               st, a.raw),
+         "vs_search_sel: merge launch");
+  return VS_OK;
+}
+
+void free_selector(vs_selector* sel) {
+  if (sel->rbits) (void)hipFree(sel->rbits);
+  if (sel->list) (void)hipFree(sel->list);
+  delete sel;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vs_selector_create(vs_index* idx, const uint8_t* bitmap, int64_t nbits, void* stream,
+                       vs_selector** out) {
+  if (!out) return fail(VS_E_INVALID, "vs_selector_create: null output");
+  *out = nullptr;
+  if (!idx) return fail(VS_E_INVALID, "vs_selector_create: null index");
+  if (nbits < 0) return fail(VS_E_INVALID, "vs_selector_create: nbits < 0");
+  if (nbits > 0 && !bitmap) return fail(VS_E_INVALID, "vs_selector_create: null bitmap");
+  hipStream_t st = (hipStream_t)stream;
+  std::shared_lock<std::shared_mutex> lk(idx->mu);
+  DeviceGuard g(idx->device);
+  if (!g.ok) return fail(VS_E_HIP, "vs_selector_create: hipSetDevice failed");
+  vs_selector* sel = new vs_selector();
+  sel->idx = idx;
+  sel->device = idx->device;
+  sel->gen = idx->gen;
+  const int64_t nb = std::min(nbits, idx->live());  // labels past ntotal are not selected
+  if (idx->ntotal == 0 || nb == 0) {
+    *out = sel;
+    return VS_OK;
+  }
+  ReaderMark mark(idx, st);
+  const int ntotal = (int)idx->ntotal;
+  const int nblocks = (ntotal + kSelBlockRows - 1) / kSelBlockRows;
+  const int64_t nwords = (int64_t)nblocks * (kSelBlockRows / 32);
+  int rc = VS_OK;
+  do {
+    hipError_t e = hipMalloc(&sel->rbits, (size_t)nwords * sizeof(uint32_t));
+    if (e != hipSuccess) { rc = hip_fail(e, "vs_selector_create: bitmap"); break; }
+    Scratch scr(st);
+    uint8_t* lbits = nullptr;
+    int* bsum = nullptr;
+    int* dcount = nullptr;
+    const size_t lbytes = (size_t)((nb + 7) / 8);
+    if ((e = scr.alloc((void**)&lbits, lbytes)) != hipSuccess ||
+        (e = scr.alloc((void**)&bsum, (size_t)nblocks * sizeof(int))) != hipSuccess ||
+        (e = scr.alloc((void**)&dcount, sizeof(int))) != hipSuccess) {
+      rc = hip_fail(e, "vs_selector_create: scratch");
+      break;
+    }
+    int hcount = 0;
+    if ((e = hipMemcpyAsync(lbits, bitmap, lbytes, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = launch_sel_row_bits(lbits, nb, idx->ddead, (int64_t)idx->dead.size(), ntotal,
+                                 sel->rbits, nwords, st)) != hipSuccess ||
+        (e = launch_sel_block_counts(sel->rbits, nblocks, bsum, st)) != hipSuccess ||
+        (e = launch_sel_scan(bsum, nblocks, dcount, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(&hcount, dcount, sizeof(int), hipMemcpyDeviceToHost, st)) !=
+            hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess) {
+      rc = hip_fail(e, "vs_selector_create: compaction");
+      break;
+    }
+    sel->count = hcount;
+    if (hcount > 0) {
+      const int64_t npad = round_up(hcount, kBN);
+      if ((e = hipMalloc(&sel->list, (size_t)npad * sizeof(int))) != hipSuccess) {
+        rc = hip_fail(e, "vs_selector_create: row list");
+        break;
+      }
+      if ((e = launch_sel_scatter(sel->rbits, nblocks, bsum, dcount, sel->list, st)) !=
+              hipSuccess ||
+          (e = hipStreamSynchronize(st)) != hipSuccess) {
+        rc = hip_fail(e, "vs_selector_create: scatter");
+        break;
+      }
+    }
+  } while (0);
+  if (rc) {
+    free_selector(sel);
+    return rc;
+  }
+  *out = sel;
+  return VS_OK;
+}
+
+int vs_selector_count(const vs_selector* sel, int64_t* out) {
+  if (!sel || !out) return fail(VS_E_INVALID, "vs_selector_count: null argument");
+  *out = sel->count;
+  return VS_OK;
+}
+
+int vs_selector_destroy(vs_selector* sel) {
+  if (!sel) return VS_OK;
+  DeviceGuard g(sel->device);
+  // the searches that read it were enqueued before this call: let them finish
+  if (sel->rbits || sel->list) (void)hipDeviceSynchronize();
+  free_selector(sel);
+  return VS_OK;
+}
+
+int vs_search_sel(vs_index* idx, const vs_selector* sel, const float* x, int64_t n, int64_t k,
+                  float* D, int64_t* I, int flags, void* stream) {
+  if (!idx) return fail(VS_E_INVALID, "vs_search_sel: null index");
+  if (!sel) return fail(VS_E_INVALID, "vs_search_sel: null selector");
+  if (n < 0) return fail(VS_E_INVALID, "vs_search_sel: n < 0");
+  if (k <= 0) return fail(VS_E_INVALID, "vs_search_sel: k must be > 0");
+  if (k > INT_MAX / 2) return fail(VS_E_INVALID, "vs_search_sel: k too large");
+  if (n == 0) return VS_OK;
+  if (!x || !D || !I) return fail(VS_E_INVALID, "vs_search_sel: null buffer");
+  hipStream_t st = (hipStream_t)stream;
+  std::shared_lock<std::shared_mutex> lk(idx->mu);
+  if (sel->idx != idx) return fail(VS_E_INVALID, "vs_search_sel: the selector belongs to another index");
+  if (sel->gen != idx->gen)
+    return fail(VS_E_INVALID, "vs_search_sel: stale selector (the index changed since it was built)");
+  DeviceGuard g(idx->device);
+  if (!g.ok) return fail(VS_E_HIP, "vs_search_sel: hipSetDevice failed");
+  ReaderMark mark(idx, st);
+  const bool out_dev = (flags & VS_OUT_DEVICE) != 0;
+  const int mode = idx->metric == VS_METRIC_L2 ? MODE_L2 : MODE_IP;
+  Scratch scr(st);
+
+  float* Dd = D;
+  int64_t* Id = I;
+  if (!out_dev) {
+    VS_HIP(scr.alloc((void**)&Dd, (size_t)n * k * sizeof(float)), "vs_search_sel: scratch");
+    VS_HIP(scr.alloc((void**)&Id, (size_t)n * k * sizeof(int64_t)), "vs_search_sel: scratch");
+  }
+  if (idx->ntotal == 0 || sel->count == 0) {
+    VS_HIP(launch_fill_empty(mode, Dd, Id, n * k, st), "vs_search_sel: fill");
+  } else {
+    // the query staging of vs_search
+    const int64_t chunk = 65536;
+    float* qbuf = nullptr;
+    float* qaux = nullptr;
+    const int64_t cmax = std::min<int64_t>(n, chunk);
+    const int64_t qrows = round_up(std::max<int64_t>(cmax, kGemvMaxQ), kBQ);
+    VS_HIP(scr.alloc((void**)&qbuf, (size_t)qrows * idx->ld * sizeof(float)),
+           "vs_search_sel: scratch");
+    VS_HIP(scr.alloc((void**)&qaux, (size_t)qrows * sizeof(float)), "vs_search_sel: scratch");
+    uint16_t* qb16 = nullptr;
+    if (idx->esize == 2)
+      VS_HIP(scr.alloc((void**)&qb16, (size_t)qrows * idx->ld * sizeof(uint16_t)),
+             "vs_search_sel: scratch");
+    const hipMemcpyKind kind =
+        (flags & VS_IN_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+      const int64_t nc = std::min(chunk, n - c0);
+      const int64_t nq_pad = round_up(std::max<int64_t>(nc, kGemvMaxQ), kBQ);
+      if (idx->d == idx->ld) {
+        if (nq_pad > nc)
+          VS_HIP(hipMemsetAsync(qbuf + nc * idx->ld, 0,
+                                (size_t)(nq_pad - nc) * idx->ld * sizeof(float), st),
+                 "vs_search_sel: zero queries");
+      } else {
+        VS_HIP(hipMemsetAsync(qbuf, 0, (size_t)nq_pad * idx->ld * sizeof(float), st),
+               "vs_search_sel: zero queries");
+      }
+      VS_HIP(hipMemcpy2DAsync(qbuf, idx->ld * sizeof(float), x + c0 * idx->d,
+                              (size_t)idx->d * sizeof(float), (size_t)idx->d * sizeof(float),
+                              (size_t)nc, kind, st),
+             "vs_search_sel: staging queries");
+      if (idx->esize == 2) {
+        VS_HIP(launch_round_bf16(qbuf, nq_pad * idx->ld, st), "vs_search_sel: rounding queries");
+        VS_HIP(launch_f32_to_bf16(qbuf, idx->ld, qb16, idx->ld, nq_pad, idx->ld, st),
+               "vs_search_sel: bf16 queries");
+      }
+      if (mode == MODE_L2)
+        VS_HIP(launch_row_norms(qbuf, 4, idx->ld, 0, nq_pad, qaux, st),
+               "vs_search_sel: query norms");
+      SearchArgs sa;
+      sa.mode = mode;
+      sa.qbuf = qbuf;
+      sa.qb16 = qb16;
+      sa.qaux = qaux;
+      sa.xaux = idx->norms;
+      sa.nq = (int)nc;
+      sa.nq_pad = (int)nq_pad;
+      sa.k = (int)k;
+      sa.raw = (flags & VS_RAW_ORDER) ? 1 : 0;
+      sa.l2_direct = n < kBlasThreshold;
+      sa.host_wait = !out_dev;
+      sa.D = Dd + c0 * k;
+      sa.I = Id + c0 * k;
+      int rc = run_selected(idx, sel, sa, n <= kSkinnyMaxQ, st);
+      if (rc) return rc;
+    }
+    if (!idx->dead.empty())
+      VS_HIP(launch_label_map(Id, n * k, idx->ddead, (int64_t)idx->dead.size(), idx->id_base, st),
+             "vs_search_sel: labels");
+  }
+  if (!out_dev) {
+    VS_HIP(hipMemcpyAsync(D, Dd, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, st),
+           "vs_search_sel: copy D");
+    VS_HIP(hipMemcpyAsync(I, Id, (size_t)n * k * sizeof(int64_t), hipMemcpyDeviceToHost, st),
+           "vs_search_sel: copy I");
+    VS_HIP(hipStreamSynchronize(st), "vs_search_sel: synchronise");
+  } else {
+    VS_HIP(hipGetLastError(), "vs_search_sel");
   }
   return VS_OK;
 }
@@ -2461,6 +2793,7 @@ int pack_dead(vs_index* idx) {
   VS_HIP(wait_readers(idx), "vs: pack");
   hipStream_t st = nullptr;
   VS_HIP(writer_stream(idx, &st), "vs: pack");
+  ++idx->gen;
   const int rc = compact_rows(idx, idx->dead, st);
   if (rc) return rc;
   idx->dead.clear();
@@ -2511,6 +2844,7 @@ int vs_remove_ids(vs_index* idx, const int64_t* ids, int64_t n, int64_t* nremove
   rm.erase(std::unique(rm.begin(), rm.end()), rm.end());
   const int64_t nrem = (int64_t)rm.size();
   if (nrem == 0) return VS_OK;
+  ++idx->gen;
   DeviceGuard g(idx->device);
   // Searches of this index already queued on other streams read the rows we
   // are about to move or overwrite: wait for their marks (not for the device).

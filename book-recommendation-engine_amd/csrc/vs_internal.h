@@ -468,4 +468,43 @@ hipError_t launch_gather_kept(const void* X, const float* norms, int64_t rowbyte
                               int64_t n, const int64_t* removed, int64_t nrem, void* tmp,
                               float* tmp_norms, hipStream_t st);
 
+// Selector searches (vs_select.hip; vs_api.hip vs_selector_create / vs_search_sel).
+// A selector is a bitmap over the rows in place (word r >> 5, bit r & 31) and
+// the ascending list of the selected rows.
+// Rows per compaction block: 256 words of 32 rows.
+constexpr int kSelBlockRows = 8192;
+// rbits[0 .. nwords) from the label bitmap (faiss IDSelectorBitmap layout over
+// labels - id_base, nbits of them): row r is selected iff it is live (not in
+// the sorted dead list) and the bit of its position among the live rows is set.
+// nwords covers whole compaction blocks; bits of rows >= ntotal are clear.
+hipError_t launch_sel_row_bits(const uint8_t* lbits, int64_t nbits, const int64_t* dead,
+                               int64_t ndead, int ntotal, uint32_t* rbits, int64_t nwords,
+                               hipStream_t st);
+// Compaction of the set bits: bsum[b] = the set bits of block b, then the
+// exclusive scan of bsum in place and *count = their total, then the scatter
+// of the set rows, ascending, to list[0 .. *count) and the padding of the list
+// to a multiple of kBN with its last row.
+hipError_t launch_sel_block_counts(const uint32_t* rbits, int nblocks, int* bsum, hipStream_t st);
+hipError_t launch_sel_scan(int* bsum, int nblocks, int* count, hipStream_t st);
+hipError_t launch_sel_scatter(const uint32_t* rbits, int nblocks, const int* boff,
+                              const int* count, int* list, hipStream_t st);
+// Route (b): the entries of Din / Iin ([nq][k_in], labels = row + id_base, -1
+// empty) whose row bit is set, in order, as the first k_out entries of every
+// query's row of Dout / Iout (padded with the empty result of `mode`).
+hipError_t launch_sel_drop(int mode, const float* Din, const int64_t* Iin, int nq, int k_in,
+                           const uint32_t* rbits, int64_t id_base, float* Dout, int64_t* Iout,
+                           int k_out, hipStream_t st);
+// gemm_topk over the rows list[0 .. count) (list padded to a multiple of kBN
+// with a valid row): the lists hold rows in place, 2 * nsplit lists per query.
+// Modes IP and L2 (norm expansion), fp32 or bf16 rows.
+hipError_t launch_gemm_topk_rows(int KP, int mode, const void* X, const float* xaux,
+                                 const void* Q, const float* qaux, int64_t ld, int esize,
+                                 const int* list, int count, int nq_pad, int nsplit,
+                                 Partials part, hipStream_t st);
+// gemv_topk over the rows list[0 .. count): modes IP and L2D, nq <= kGemvMaxQ,
+// one list per query per block (part.P == nblocks).
+hipError_t launch_gemv_topk_rows(int KP, int mode, int nq, const void* X, int esize,
+                                 const float* Q, int64_t ld, const int* list, int count,
+                                 int nblocks, Partials part, hipStream_t st);
+
 }  // namespace vs

@@ -60,6 +60,10 @@ SIGNATURES = {
     "vs_filter_plane": (_c_int, [_vp, ctypes.POINTER(_c_int)]),
     "vs_notice": (ctypes.c_char_p, [_vp]),
     "vs_search": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp]),
+    "vs_selector_create": (_c_int, [_vp, _vp, _c_i64, _vp, ctypes.POINTER(_vp)]),
+    "vs_selector_count": (_c_int, [_vp, _i64p]),
+    "vs_selector_destroy": (_c_int, [_vp]),
+    "vs_search_sel": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp]),
     "vs_reconstruct_n": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _vp]),
     "vs_remove_ids": (_c_int, [_vp, _vp, _c_i64, _i64p]),
     "vs_selfjoin": (

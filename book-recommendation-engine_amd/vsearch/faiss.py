@@ -14,6 +14,10 @@ not vendored) that the reference reaches through LangChain's ``FAISS`` store:
 * ``index.remove_ids`` (via ``FAISS.delete``)
 * ``write_index`` / ``read_index`` (via ``save_local`` / ``load_local``)
 * ``normalize_L2`` (LangChain's ``normalize_L2=True`` option)
+* ``index.search(x, k, params=SearchParameters(sel=IDSelector...))`` — the k
+  nearest rows among the selected labels, in place of the reference's
+  search-``k * 2``-then-drop loops (candidate_builder.py:187-203,
+  service.py:529-542,627-640)
 
 Argument checks mirror faiss's python wrapper (``assert d == self.d``,
 ``assert k > 0``); library failures raise ``RuntimeError`` subclasses.
@@ -38,7 +42,18 @@ __all__ = [
     "IndexFlat",
     "IndexFlatIP",
     "IndexFlatL2",
+    "IDSelector",
+    "IDSelectorAll",
+    "IDSelectorAnd",
+    "IDSelectorArray",
     "IDSelectorBatch",
+    "IDSelectorBitmap",
+    "IDSelectorNot",
+    "IDSelectorOr",
+    "IDSelectorRange",
+    "SearchParameters",
+    "Selector",
+    "selector_bitmap",
     "normalize_L2",
     "read_index",
     "write_index",
@@ -75,6 +90,158 @@ class IDSelectorBatch:
         return bool(np.isin(i, self.ids))
 
 
+class IDSelector:
+    """faiss.IDSelector: a predicate over labels.  ``is_member(i)`` as faiss;
+    ``members(labels)`` is the same over an int64 array (a bool array)."""
+
+    def members(self, labels: np.ndarray) -> np.ndarray:
+        raise NotImplementedError
+
+    def is_member(self, i: int) -> bool:
+        return bool(self.members(np.asarray([i], dtype=np.int64))[0])
+
+
+def _members(sel, labels: np.ndarray) -> np.ndarray:
+    if hasattr(sel, "members"):
+        return np.asarray(sel.members(labels), dtype=bool)
+    if isinstance(sel, IDSelectorBatch):
+        return np.isin(labels, sel.ids)
+    return np.fromiter((bool(sel.is_member(int(i))) for i in labels), dtype=bool,
+                       count=len(labels))
+
+
+class IDSelectorAll(IDSelector):
+    """faiss.IDSelectorAll: every label."""
+
+    def members(self, labels):
+        return np.ones(len(labels), dtype=bool)
+
+
+class IDSelectorRange(IDSelector):
+    """faiss.IDSelectorRange: labels in [imin, imax) (half-open, as faiss)."""
+
+    def __init__(self, imin: int, imax: int, assume_sorted: bool = False):
+        self.imin = int(imin)
+        self.imax = int(imax)
+        self.assume_sorted = bool(assume_sorted)
+
+    def members(self, labels):
+        labels = np.asarray(labels, dtype=np.int64)
+        return (labels >= self.imin) & (labels < self.imax)
+
+
+class IDSelectorArray(IDSelector):
+    """faiss.IDSelectorArray: the labels of an array (duplicates allowed)."""
+
+    def __init__(self, ids):
+        self.ids = np.ascontiguousarray(ids, dtype="int64").ravel()
+
+    def members(self, labels):
+        return np.isin(np.asarray(labels, dtype=np.int64), self.ids)
+
+
+class IDSelectorBitmap(IDSelector):
+    """faiss.IDSelectorBitmap: label i is selected iff bit (i & 7) of byte
+    (i >> 3) is set; n is the number of bits given (labels past it are not
+    selected)."""
+
+    def __init__(self, n: int, bitmap):
+        self.n = int(n)
+        self.bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8).ravel()
+        assert self.bitmap.size * 8 >= self.n
+
+    def members(self, labels):
+        labels = np.asarray(labels, dtype=np.int64)
+        ok = (labels >= 0) & (labels < self.n)
+        safe = np.where(ok, labels, 0)
+        if self.bitmap.size == 0:
+            return np.zeros(len(labels), dtype=bool)
+        bits = (self.bitmap[safe >> 3] >> (safe & 7).astype(np.uint8)) & 1
+        return ok & (bits != 0)
+
+
+class IDSelectorNot(IDSelector):
+    """faiss.IDSelectorNot."""
+
+    def __init__(self, sel):
+        self.sel = sel
+
+    def members(self, labels):
+        return ~_members(self.sel, labels)
+
+
+class IDSelectorAnd(IDSelector):
+    """faiss.IDSelectorAnd."""
+
+    def __init__(self, lhs, rhs):
+        self.lhs = lhs
+        self.rhs = rhs
+
+    def members(self, labels):
+        return _members(self.lhs, labels) & _members(self.rhs, labels)
+
+
+class IDSelectorOr(IDSelector):
+    """faiss.IDSelectorOr."""
+
+    def __init__(self, lhs, rhs):
+        self.lhs = lhs
+        self.rhs = rhs
+
+    def members(self, labels):
+        return _members(self.lhs, labels) | _members(self.rhs, labels)
+
+
+def selector_bitmap(sel, ntotal: int, id_base: int = 0) -> np.ndarray:
+    """The label bitmap of a selector tree for an index of ``ntotal`` rows whose
+    labels start at ``id_base``: uint8, (ntotal + 7) // 8 bytes, bit i (faiss
+    IDSelectorBitmap layout) set iff ``sel.is_member(id_base + i)``."""
+    ntotal = int(ntotal)
+    labels = np.arange(int(id_base), int(id_base) + ntotal, dtype=np.int64)
+    mask = _members(sel, labels) if ntotal else np.zeros(0, dtype=bool)
+    return np.packbits(mask, bitorder="little")
+
+
+class SearchParameters:
+    """faiss.SearchParameters: ``sel`` restricts a search to the selected labels
+    (an IDSelector tree, or a ``Selector`` built once by ``index.selector``)."""
+
+    def __init__(self, sel=None):
+        self.sel = sel
+
+
+class Selector:
+    """Device handle of a selection of one index (``IndexFlat.selector``):
+    reusable across searches until the index changes (add, remove_ids, reset),
+    after which searching with it raises RuntimeError ("stale selector")."""
+
+    def __init__(self, index: "IndexFlat", bitmap: np.ndarray, nbits: int):
+        self._lib = index._lib
+        self._h = ctypes.c_void_p()
+        self.index = index
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
+        assert bitmap.size * 8 >= nbits
+        _lib.check(self._lib.vs_selector_create(index._h, bitmap.ctypes.data if bitmap.size else None,
+                                                int(nbits), None, ctypes.byref(self._h)),
+                   "vs_selector_create")
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.vs_selector_count(self._h, ctypes.byref(n)), "vs_selector_count")
+        self.count = int(n.value)
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h is None or not h.value:
+            return
+        try:
+            self._lib.vs_selector_destroy(h)
+        except Exception:  # interpreter shutdown: the library may be gone
+            pass
+        h.value = None
+
+    def __del__(self):
+        self.close()
+
+
 class Index:
     """Common base (faiss.Index)."""
 
@@ -104,6 +271,7 @@ class IndexFlat(Index):
         self._d = d
         self._metric = int(metric)
         self._dtype = "bf16" if code == _lib.DTYPE_BF16 else "f32"
+        self._id_base = 0
 
     # -- attributes faiss exposes -------------------------------------------------
     @property
@@ -220,10 +388,32 @@ class IndexFlat(Index):
 
     def set_id_base(self, base: int) -> None:
         _lib.check(self._lib.vs_set_id_base(self._h, int(base)), "vs_set_id_base")
+        self._id_base = int(base)
+
+    def selector(self, sel) -> Selector:
+        """The device handle of a selection: ``sel`` is an IDSelector tree over
+        this index's labels.  ``.count`` is the number of selected rows."""
+        if isinstance(sel, Selector):
+            return sel
+        ntotal = self.ntotal
+        return Selector(self, selector_bitmap(sel, ntotal, self._id_base), ntotal)
+
+    def _resolve_selector(self, sel):
+        """(handle, owned): a Selector as it is, a selector tree built for this call."""
+        if isinstance(sel, Selector):
+            if sel.index is not self:
+                raise ValueError("the Selector belongs to another index")
+            return sel, False
+        return self.selector(sel), True
 
     # -- queries -----------------------------------------------------------------------
-    def search(self, x, k, *, D=None, I=None, raw: bool = False):
+    def search(self, x, k, *, params=None, D=None, I=None, raw: bool = False):
         """faiss Index.search: returns (D float32 (n,k), I int64 (n,k)).
+
+        ``params=SearchParameters(sel=...)`` restricts the search to the selected
+        labels (an IDSelector tree, built and freed in this call, or a
+        ``Selector`` from ``index.selector``, reused); fewer than k selected
+        rows pad with label -1.
 
         ``raw=True`` returns the k lexicographically best (key, label) entries
         instead of faiss's inner-product tie order (VS_RAW_ORDER; the per-shard
@@ -243,19 +433,41 @@ class IndexFlat(Index):
             assert I.shape == (n, k)
         if n == 0:
             return D, I
+        sel = getattr(params, "sel", None) if params is not None else None
+        if sel is not None:
+            handle, owned = self._resolve_selector(sel)
+            try:
+                _lib.check(self._lib.vs_search_sel(self._h, handle._h, x.ctypes.data, n, k,
+                                                   D.ctypes.data, I.ctypes.data,
+                                                   _lib.RAW_ORDER if raw else 0, None),
+                           "vs_search_sel")
+            finally:
+                if owned:
+                    handle.close()
+            return D, I
         _lib.check(self._lib.vs_search(self._h, x.ctypes.data, n, k, D.ctypes.data,
                                        I.ctypes.data, _lib.RAW_ORDER if raw else 0, None),
                    "vs_search")
         return D, I
 
     def search_device(self, xq_ptr: int, n: int, k: int, D_ptr: int, I_ptr: int,
-                      stream: int = 0, raw: bool = False) -> None:
+                      stream: int = 0, raw: bool = False, selector=None) -> None:
         """Device-resident search: all buffers are device pointers on this index's
         device; stream-ordered on `stream` (a hipStream_t, 0 = default stream).
         Returns once the first filter stage's count of unsettled queries is read
         (later stages are enqueued only for queries left; VS_TAIL_WAIT=0 keeps
         the call fully asynchronous)."""
         flags = _lib.IN_DEVICE | _lib.OUT_DEVICE | (_lib.RAW_ORDER if raw else 0)
+        if selector is not None:
+            # a Selector only: a handle built for this call could not be freed
+            # before the stream has run the search
+            if not isinstance(selector, Selector) or selector.index is not self:
+                raise ValueError("search_device takes a Selector of this index")
+            _lib.check(self._lib.vs_search_sel(self._h, selector._h, ctypes.c_void_p(xq_ptr),
+                                               int(n), int(k), ctypes.c_void_p(D_ptr),
+                                               ctypes.c_void_p(I_ptr), flags,
+                                               ctypes.c_void_p(stream)), "vs_search_sel")
+            return
         _lib.check(self._lib.vs_search(self._h, ctypes.c_void_p(xq_ptr), int(n), int(k),
                                        ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags,
                                        ctypes.c_void_p(stream)), "vs_search")

@@ -200,6 +200,8 @@ class FAISS:
         self._normalize_L2 = normalize_L2
         self._keymap_field: Optional[str] = None  # metadata field indexed by _key_index
         self._keymap: Dict[Any, List[str]] = {}
+        # exact_filter selectors by the filter's JSON; dropped by every add / delete / merge
+        self._sel_cache: Dict[str, Any] = {}
         if (self.distance_strategy != DistanceStrategy.EUCLIDEAN_DISTANCE
                 and self._normalize_L2):
             warnings.warn(
@@ -241,6 +243,7 @@ class FAISS:
             vector = vector.reshape(len(documents), -1)
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
+        self._sel_cache.clear()
         self.index.add(vector)
         self.docstore.add({id_: doc for id_, doc in zip(ids, documents)})
         starting_len = len(self.index_to_docstore_id)
@@ -339,6 +342,7 @@ class FAISS:
                 f"{missing_ids}")
         reversed_index = {id_: idx for idx, id_ in self.index_to_docstore_id.items()}
         index_to_delete = {reversed_index[id_] for id_ in ids}
+        self._sel_cache.clear()
         self.index.remove_ids(np.fromiter(index_to_delete, dtype=np.int64))
         if self._keymap_field is not None:
             for id_ in ids:
@@ -363,6 +367,7 @@ class FAISS:
         if not hasattr(self.docstore, "add"):
             raise ValueError("Cannot merge with this type of docstore")
         index_offset = len(self.index_to_docstore_id)
+        self._sel_cache.clear()
         if target.index.ntotal:
             self.index.add(target.index.reconstruct_n(0, target.index.ntotal))
         full_info = []
@@ -374,14 +379,103 @@ class FAISS:
         self.docstore.add({_id: doc for _, _id, doc in full_info})
         self.index_to_docstore_id.update({index: _id for index, _id, _ in full_info})
 
+    # -- exact filters ------------------------------------------------------------------------
+    def _filter_mask(self, filter: Any, use_key_index: bool = True) -> np.ndarray:
+        """The labels (bool array over 0 .. ntotal) whose document passes `filter`.
+        A dict on one field with $eq / $in / $nin / $neq, a bare value or a list
+        is answered from ``_key_index(field)`` without reading the docstore;
+        other dicts and callables scan the docstore once."""
+        n = len(self.index_to_docstore_id)
+        mask = np.zeros(n, dtype=bool)
+        fast = self._key_index_values(filter) if use_key_index else None
+        if fast is not None:
+            field, values, negate = fast
+            keymap = self._key_index(field)
+            label_of = {id_: i for i, id_ in self.index_to_docstore_id.items()}
+            for v in values:
+                for id_ in keymap.get(v, ()):
+                    mask[label_of[id_]] = True
+            return ~mask if negate else mask
+        filter_func = _create_filter_func(filter)
+        for i, id_ in self.index_to_docstore_id.items():
+            doc = self.docstore.search(id_)
+            if isinstance(doc, Document) and filter_func(doc.metadata):
+                mask[i] = True
+        return mask
+
+    @staticmethod
+    def _key_index_values(filter: Any):
+        """(field, values, negate) when `filter` is a one-field membership test the
+        key index answers, else None.  None values and unhashable ones are left
+        to the scan (the key index does not hold documents without the field)."""
+        if not isinstance(filter, dict) or len(filter) != 1:
+            return None
+        (field, cond), = filter.items()
+        if not isinstance(field, str) or field.startswith("$"):
+            return None
+        negate = False
+        if isinstance(cond, dict):
+            if len(cond) != 1:
+                return None
+            (op, value), = cond.items()
+            if op in ("$eq", "$neq"):
+                values = [value]
+            elif op in ("$in", "$nin"):
+                if not isinstance(value, (list, tuple, set, frozenset)):
+                    return None
+                values = list(value)
+            else:
+                return None
+            negate = op in ("$neq", "$nin")
+        elif isinstance(cond, list):
+            values = cond
+        else:
+            values = [cond]
+        try:
+            if any(v is None for v in values):
+                return None
+            set(values)  # hashable
+        except TypeError:
+            return None
+        return field, values, negate
+
+    def _filter_selector(self, filter: Any):
+        """What ``index.search(params=SearchParameters(sel=...))`` takes for
+        `filter`: the index's device handle where it has one (built once per
+        filter, kept until the store changes), else the label bitmap."""
+        key = None
+        if not callable(filter):
+            try:
+                key = json.dumps(filter, sort_keys=True, default=repr)
+            except (TypeError, ValueError):
+                key = None
+        if key is not None and key in self._sel_cache:
+            return self._sel_cache[key]
+        mask = self._filter_mask(filter)
+        sel = vfaiss.IDSelectorBitmap(mask.size, np.packbits(mask, bitorder="little"))
+        if hasattr(self.index, "selector"):
+            sel = self.index.selector(sel)
+        if key is not None:
+            self._sel_cache[key] = sel
+        return sel
+
     # -- reads ------------------------------------------------------------------------------
     def similarity_search_with_score_by_vector(self, embedding: List[float], k: int = 4,
                                                filter: Optional[Any] = None, fetch_k: int = 20,
+                                               exact_filter: bool = False,
                                                **kwargs: Any) -> List[Tuple[Document, float]]:
+        """``exact_filter=True``: the k nearest documents among those that pass
+        `filter` (exactly min(k, matches) of them; `fetch_k` is ignored), by a
+        selector search, instead of filtering the `fetch_k` nearest on the host."""
         vector = np.array([embedding], dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
-        scores, indices = self.index.search(vector, k if filter is None else fetch_k)
+        if exact_filter and filter is not None:
+            scores, indices = self.index.search(
+                vector, k, params=vfaiss.SearchParameters(sel=self._filter_selector(filter)))
+            filter = None  # every label returned passes it
+        else:
+            scores, indices = self.index.search(vector, k if filter is None else fetch_k)
         docs = []
         filter_func = _create_filter_func(filter) if filter is not None else None
         for j, i in enumerate(indices[0]):
@@ -401,21 +495,24 @@ class FAISS:
         return docs[:k]
 
     def similarity_search_with_score(self, query: str, k: int = 4, filter: Optional[Any] = None,
-                                     fetch_k: int = 20, **kwargs: Any):
+                                     fetch_k: int = 20, exact_filter: bool = False,
+                                     **kwargs: Any):
         embedding = self._embed_query(query)
         return self.similarity_search_with_score_by_vector(embedding, k, filter=filter,
-                                                           fetch_k=fetch_k, **kwargs)
+                                                           fetch_k=fetch_k,
+                                                           exact_filter=exact_filter, **kwargs)
 
     def similarity_search_by_vector(self, embedding: List[float], k: int = 4,
                                     filter: Optional[Any] = None, fetch_k: int = 20,
-                                    **kwargs: Any) -> List[Document]:
+                                    exact_filter: bool = False, **kwargs: Any) -> List[Document]:
         return [d for d, _ in self.similarity_search_with_score_by_vector(
-            embedding, k, filter=filter, fetch_k=fetch_k, **kwargs)]
+            embedding, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
 
     def similarity_search(self, query: str, k: int = 4, filter: Optional[Any] = None,
-                          fetch_k: int = 20, **kwargs: Any) -> List[Document]:
+                          fetch_k: int = 20, exact_filter: bool = False,
+                          **kwargs: Any) -> List[Document]:
         return [d for d, _ in self.similarity_search_with_score(
-            query, k, filter=filter, fetch_k=fetch_k, **kwargs)]
+            query, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
 
     def similarity_search_batch_by_vector(self, embeddings, k: int = 4):
         """Batched variant (one engine call for many queries): list of
@@ -449,11 +546,11 @@ class FAISS:
 
     def similarity_search_with_relevance_scores(self, query: str, k: int = 4,
                                                 filter: Optional[Any] = None, fetch_k: int = 20,
-                                                **kwargs: Any):
+                                                exact_filter: bool = False, **kwargs: Any):
         fn = self._select_relevance_score_fn()
         score_threshold = kwargs.pop("score_threshold", None)
         docs = self.similarity_search_with_score(query, k=k, filter=filter, fetch_k=fetch_k,
-                                                 **kwargs)
+                                                 exact_filter=exact_filter, **kwargs)
         out = [(doc, fn(score)) for doc, score in docs]
         if score_threshold is not None:
             out = [(d, s) for d, s in out if s >= score_threshold]

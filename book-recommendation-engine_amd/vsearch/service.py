@@ -350,6 +350,12 @@ class IndexService:
         st = self.store
         k = int(h.get("k", 4))
         flt = h.get("filter")
+        if h.get("exact_filter") and flt is not None:
+            # a selector search runs on its own: the coalescer stacks callers
+            # that share one k and no selector
+            docs = self._read(st.similarity_search_with_score_by_vector, vec[0], k, filter=flt,
+                              exact_filter=True, score_threshold=h.get("score_threshold"))
+            return [[d.to_json(), float(s)] for d, s in docs]
         if st._normalize_L2:
             from . import faiss as vfaiss
             vfaiss.normalize_L2(vec)
@@ -447,27 +453,30 @@ class RemoteFAISS:
         return self._results(self._call(header, payload)[0])
 
     def similarity_search_with_score_by_vector(self, embedding, k: int = 4, filter=None,
-                                               fetch_k: int = 20, **kwargs):
+                                               fetch_k: int = 20, exact_filter: bool = False,
+                                               **kwargs):
         v = np.ascontiguousarray(np.asarray([embedding], dtype=np.float32))
         return self._search({"op": "similarity_search_with_score", "k": k, "filter": filter,
-                             "fetch_k": fetch_k, "score_threshold": kwargs.get("score_threshold"),
+                             "fetch_k": fetch_k, "exact_filter": bool(exact_filter),
+                             "score_threshold": kwargs.get("score_threshold"),
                              "shape": list(v.shape)}, v.astype("<f4").tobytes())
 
     def similarity_search_with_score(self, query: str, k: int = 4, filter=None,
-                                     fetch_k: int = 20, **kwargs):
+                                     fetch_k: int = 20, exact_filter: bool = False, **kwargs):
         return self._search({"op": "similarity_search_with_score", "query": query, "k": k,
                              "filter": filter, "fetch_k": fetch_k,
+                             "exact_filter": bool(exact_filter),
                              "score_threshold": kwargs.get("score_threshold")})
 
     def similarity_search_by_vector(self, embedding, k: int = 4, filter=None, fetch_k: int = 20,
-                                    **kwargs) -> List[Document]:
+                                    exact_filter: bool = False, **kwargs) -> List[Document]:
         return [d for d, _ in self.similarity_search_with_score_by_vector(
-            embedding, k, filter=filter, fetch_k=fetch_k, **kwargs)]
+            embedding, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
 
     def similarity_search(self, query: str, k: int = 4, filter=None, fetch_k: int = 20,
-                          **kwargs) -> List[Document]:
+                          exact_filter: bool = False, **kwargs) -> List[Document]:
         return [d for d, _ in self.similarity_search_with_score(
-            query, k, filter=filter, fetch_k=fetch_k, **kwargs)]
+            query, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
 
     def get_by_ids(self, ids: Sequence[str]) -> List[Document]:
         return [Document.from_json(d) for d in self._call({"op": "get_by_ids",

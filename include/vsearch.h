@@ -174,6 +174,42 @@ int vs_set_id_base(vs_index* idx, int64_t id_base);
 int vs_search(vs_index* idx, const float* x, int64_t n, int64_t k, float* D, int64_t* I,
               int flags, void* stream);
 
+/* ---- selector searches -----------------------------------------------------
+ * faiss index.search(x, k, params=SearchParameters(sel=IDSelector...)): the k
+ * nearest rows among the selected labels only.  Replaces the reference's
+ * over-fetch-then-drop loops (search k * 2, drop the books a student has read:
+ * src/recommendation_api/candidate_builder.py:187-203, service.py:529-542,
+ * 627-640) and LangChain's host-side `filter=` over fetch_k rows
+ * (candidate_builder.py:150-153), which return fewer than k when the nearest
+ * rows are mostly excluded.
+ *
+ * A selector belongs to one index and is reusable across searches.  bitmap is
+ * HOST bytes in faiss's IDSelectorBitmap layout: label l is selected iff bit
+ * ((l - id_base) & 7) of byte ((l - id_base) >> 3) is set; nbits bits are
+ * given, labels past nbits or past ntotal are not selected.  Anything that
+ * moves rows or changes labels (vs_add, vs_remove_ids, vs_reset,
+ * vs_set_id_base to another base) makes the selector stale. */
+typedef struct vs_selector vs_selector;
+int vs_selector_create(vs_index* idx, const uint8_t* bitmap, int64_t nbits, void* stream,
+                       vs_selector** out);
+/* The selected live rows. */
+int vs_selector_count(const vs_selector* sel, int64_t* out);
+int vs_selector_destroy(vs_selector* sel);
+/* vs_search restricted to the selector's rows: same outputs, padding (fewer
+ * than k selected rows pad with (+FLT_MAX | -FLT_MAX, -1)), tie rules (over the
+ * selected rows only), flags (VS_IN_DEVICE / VS_OUT_DEVICE / VS_RAW_ORDER) and
+ * stream contract.  A selector built before the index last changed:
+ * VS_E_INVALID ("stale selector").  Selections that leave at most 256 live rows
+ * out run the unselected engine for k plus the excluded rows and drop those
+ * (any k); every other selection runs the gathered kernels over the selected
+ * rows alone, one exact page: inner product k <= 32, L2 / VS_RAW_ORDER k <= 64,
+ * VS_E_UNSUPPORTED past it.  L2 on the gathered streaming kernel (calls of at
+ * most 32 queries) is faiss's sequential sum (x - q)^2 — the branch faiss-cpu
+ * 1.11 takes for a search with a selector (distances.cpp knn_L2sqr, as
+ * recalled: faiss is not vendored); larger calls use |q|^2 + |x|^2 - 2 q.x. */
+int vs_search_sel(vs_index* idx, const vs_selector* sel, const float* x, int64_t n, int64_t k,
+                  float* D, int64_t* I, int flags, void* stream);
+
 /* faiss Index::reconstruct_n(i0, n, out) / reconstruct(i) — rows as added
  * (bf16 storage returns the stored bf16 value widened to float32).
  * Callers: store.index.reconstruct at candidate_builder.py:166-168, service.py:490-494. */
