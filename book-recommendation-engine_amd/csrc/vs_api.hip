@@ -1194,7 +1194,7 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
                            : make_bound_args(idx->ld, plane);
   if (!gathered && !small && x1_dump_applies(kmode, plane) && dump_enabled() &&
       x1_pass_dumps(ntotal, x.nsplit)) {
-    // query cuts + dump launches (vs_gemm_x1.hip header and "Query cuts"): the
+    // query cuts + dump launches (vs_gemm_x1.hip header, vs_x1_cuts.hip "Query cuts"): the
     // cuts are set after the pass's first launch and are the verification's
     // floor for the rows the dump launches drop.  The dump slots: up to
     // x1_dump_slots() candidate rows per lane list and segment within ~4 GB;
@@ -3078,6 +3078,15 @@ int vs_filter_exact_stats(int64_t* streamed) {
 int vs_x1_stamps(unsigned long long* out, int reset) {
   if (!out) return fail(VS_E_INVALID, "vs_x1_stamps: null buffer");
   VS_HIP(x1_stamps(out, reset), "vs_x1_stamps");
+  return VS_OK;
+}
+
+int vs_x1_plan(int mode, int filter, int64_t ntotal, int nsplit, int can_dump, int ecut,
+               int gathered, int recut, int32_t* out, int cap, int* nlaunch) {
+  if (!out || !nlaunch || cap < 0) return fail(VS_E_INVALID, "vs_x1_plan: null output");
+  if (!x1_plan_describe(mode, filter, ntotal, nsplit, can_dump != 0, ecut != 0, gathered != 0,
+                        recut, dump_mfma32(), out, cap, nlaunch))
+    return fail(VS_E_INVALID, "vs_x1_plan: no such pass");
   return VS_OK;
 }
 

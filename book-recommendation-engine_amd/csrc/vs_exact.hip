@@ -8,7 +8,7 @@
 // a row spaced below the fp32 GEMM's rounding) cannot be proven from any
 // fp32 candidate list of KF rows; this kernel ranks EVERY row by the exact key
 // the rescoring computes — fp64 sums of the fp32 products (exact products),
-// rounded once, then the metric's key formula (vs_gemm_x1.hip exact_key) —
+// rounded once, then the metric's key formula (vs_x1_device.h exact_key) —
 // so its lists are the answer itself, with no bound.  Each lane sums the
 // 16-B chunks c = lane, lane + 64, ... of a row with fma in element order and
 // the wave reduces by xor-shuffles 32 .. 1: wave_dot's order, so a row's key is

@@ -1,5 +1,5 @@
-// Internal declarations shared by vs_kernels.hip (device code + launchers) and
-// vs_api.hip (the C-ABI).  Nothing here is part of the public ABI.
+// Internal declarations shared by the kernel units (vs_*.hip: device code +
+// launchers) and vs_api.hip (the C-ABI).  Nothing here is part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -136,7 +136,7 @@ struct X1Args {
   const double* qbkey = nullptr; // per query: the verification's bound B (x1_qcut)
   int qcut_m = 0;                // the M of the verification
   int recut = 1;                 // cuts after every replay: 0 set once, 1 fused, 2 replay + x1_qcut
-  // Exact-key cuts (vs_gemm_x1.hip "Exact-key cuts"; int8 inner-product passes
+  // Exact-key cuts (vs_x1_cuts.hip "Exact-key cuts"; int8 inner-product passes
   // over fp32 rows): every cut is also lowered to e_M + 1.000001 B.  ecut_x = the
   // fp32 rows (null: a_M + 2B alone), ecut_q = the stage's fp32 queries, both of
   // stride ecut_ld; qam / ecut_key / ecut_id = scratch (per query: the last
@@ -178,11 +178,16 @@ int x1_lane_len();
 // [2 groups][9 segments + 3 epilogue counts] + steps per group); zeros in a
 // real build.
 hipError_t x1_stamps(unsigned long long* out, int reset);
+// Diagnostic: the launch plan of a pass (x1_plan, vs_gemm_x1.hip) in
+// vs_x1_plan's layout (include/vsearch.h); touches no device.  dump32 as in
+// X1Args.  False for arguments no pass can have.
+bool x1_plan_describe(int mode, int filter, int64_t ntotal, int nsplit, bool can_dump, bool ecut,
+                      bool gathered, int recut, bool dump32, int32_t* out, int cap, int* nlaunch);
 // Writes 4*nsplit lists of part.KP entries per query (nq_pad queries), each holding
 // x1_lane_len() entries and empty padding.  *ndispatch = kernel launches used.
 hipError_t launch_gemm_topk_x1(int mode, const X1Args& a, Partials part, hipStream_t st,
                                int* ndispatch);
-// Bound constants of the verification (vs_gemm_x1.hip).
+// Bound constants of the verification (vs_x1_verify.hip).
 struct BoundArgs {
   int filter = FILTER_BF16;
   double gam = 0.0;       // relative error of the filter's own arithmetic (bf16: fp32
@@ -350,7 +355,7 @@ hipError_t launch_verify_wide(int mode, int nq_max, const int* qlist, const int*
                               const float* xinv, const float* qsc, const float* Dk,
                               const int64_t* Ik, unsigned long long* sizes = nullptr,
                               const float* qcut = nullptr, int xesize = 4);
-// Query cuts and dump launches of the filter pass (vs_gemm_x1.hip, "Query
+// Query cuts and dump launches of the filter pass (vs_x1_cuts.hip, "Query
 // cuts"): bkey[q] = the verification's bound B of query q; x1_dump_applies:
 // the pass of this mode and plane has a dump form (launch_gemm_topk_x1 then
 // sets the cuts after its first launch and dumps in the others; the host runs
@@ -380,7 +385,7 @@ hipError_t launch_merge_parts(int mode, const float* Dp, const int64_t* Ip, int 
 // slots[s0 .. s0 + min(*count - s0, nslot)) of a query batch whose rows sit at
 // Q + slot * ld (aux values qaux[slot]: |q|^2 for L2, 1/|q| for cosine; qrow[slot]:
 // the row to exclude, or -1; qrow may be null), the top-KP of every row by the
-// rescoring's exact key (fp64 sums, vs_gemm_x1.hip exact_key), as part.P lists
+// rescoring's exact key (fp64 sums, vs_x1_device.h exact_key), as part.P lists
 // per slot (part.P row blocks).  NQ queries per group: exact_stream_nq(ld)
 // (0: ld too large for the LDS staging).
 struct ExactStreamArgs {

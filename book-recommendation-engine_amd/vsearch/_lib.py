@@ -83,6 +83,9 @@ SIGNATURES = {
     "vs_timer_read_kernel_share": (_c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                                             _i64p, ctypes.POINTER(ctypes.c_double)]),
     "vs_x1_stamps": (_c_int, [ctypes.POINTER(ctypes.c_ulonglong), _c_int]),
+    "vs_x1_plan": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int,
+                            ctypes.POINTER(ctypes.c_int32), _c_int,
+                            ctypes.POINTER(ctypes.c_int)]),
     "vs_filter_stats": (_c_int, [_i64p, _i64p, _c_int]),
     "vs_filter_wide_stats": (_c_int, [_i64p]),
     "vs_filter_second_stats": (_c_int, [_i64p]),

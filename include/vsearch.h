@@ -287,6 +287,26 @@ int vs_timer_reset(void);
  * factor-load paths, inserting blocks, inserts]
  * then the steps of each group; reset != 0 clears them. */
 int vs_x1_stamps(unsigned long long* out, int reset);
+/* Diagnostic only (no reference interface; touches no device): the launches
+ * of one filter pass over ntotal rows in nsplit workgroup splits, as the
+ * library would run it under the environment's VS_X1_* knobs.  mode: the
+ * kernel mode (0 inner product, 1 L2, 2 cosine); filter: 0 the bf16 plane,
+ * 1 int8; can_dump: the search gave the pass dump buffers and cuts; ecut: its
+ * cuts are also exact-key cuts; gathered: a later stage's gathered batch;
+ * recut: 0 one cut per pass, 1 or 2 a new cut after every replay but the last.
+ * out holds 5 + 4 cap values:
+ *   out[0] parts the pass cuts every workgroup's tiles into, out[1] the first
+ *   launch's lists set cuts, out[2] launch 0 is a hybrid launch, out[3] the
+ *   launches after the first are dump launches, out[4] the same question as
+ *   the search asks it before allocating dump buffers (from ntotal and nsplit
+ *   alone: equal to out[3] of the call with can_dump = 1, gathered = 0);
+ *   then {p0, p1, kind, after} per launch, the first min(cap, *nlaunch):
+ *   parts [p0, p1); kind 0 list, 1 hybrid, 2 dump on 32x32x32 MFMAs, 3 dump on
+ *   16x16x64; after, a mask of what runs next in this order: 1 replay,
+ *   2 the first cut, 4 replay and a new cut, 8 an exact-key cut.
+ * *nlaunch = the pass's launches. */
+int vs_x1_plan(int mode, int filter, int64_t ntotal, int nsplit, int can_dump, int ecut,
+               int gathered, int recut, int32_t* out, int cap, int* nlaunch);
 int vs_timer_read(double* total_ms, int64_t* launches);
 /* The same for the spans of one kernel name only (the filter engine's first
  * stage is "gemm_topk_x1_i8" or "gemm_topk_x1" (bf16) per search; its first

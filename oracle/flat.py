@@ -218,7 +218,7 @@ U32 = 2.0 ** -24  # unit roundoff of fp32
 def key_window(metric: int, s, qn2, xn2, d: int, cosine: bool = False):
     """How far an engine key that is the fp32 ROUNDING of an exactly computed
     score can sit from the fp64 score s (the filter-and-verify engine: fp64 sums
-    of the fp32 products, rounded once; vs_gemm_x1.hip exact_key; fp64-summed
+    of the fp32 products, rounded once; vs_x1_device.h exact_key; fp64-summed
     norms, vs_support.hip row_norms_kernel):
       IP      key = fl(s):                          U|s|
       L2      key = fl(fl(fl(|q|^2) + fl(|x|^2)) - 2 fl(s)), clamped at 0:

@@ -1,5 +1,5 @@
-"""CPU model of the query cuts taken again after every replay (vs_gemm_x1.hip
-"Query cuts", x1_launch, x1_replay_cut_kernel).
+"""CPU model of the query cuts taken again after every replay (vs_x1_cuts.hip
+"Query cuts", x1_replay_cut_kernel; vs_gemm_x1.hip x1_plan).
 
 tests/test_filter_argument.py models ONE cut, a_M(snapshot) + 2.000001 B, taken
 after the first launch of a pass.  The pass now takes it again after every

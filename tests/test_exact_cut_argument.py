@@ -1,4 +1,4 @@
-"""CPU model of the exact-key cuts (vs_gemm_x1.hip "Exact-key cuts",
+"""CPU model of the exact-key cuts (vs_x1_cuts.hip "Exact-key cuts",
 x1_ecut_kernel).
 
 tests/test_cut_refresh_argument.py models cut = min(cut, a_M + 2.000001 B) taken

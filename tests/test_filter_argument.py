@@ -93,7 +93,7 @@ def test_wide_check_rejects_a_list_full_of_ties():
 
 
 # ---------------------------------------------------------------------------
-# The int8 filter plane's bound (vs_gemm_x1.hip quantize_i8_kernel,
+# The int8 filter plane's bound (vs_x1_planes.hip quantize_i8_kernel,
 # bound_key, make_bound_args): codes c = rint(x / s) clamped to +-127 with one
 # fp32 scale s = max|x| / 127 per row; the kernel's approximate inner product is
 # fl(fl(float(c_q . c_x)) * fl(s_q * s_x)) (exact int32 sum).  This restates
@@ -179,7 +179,7 @@ def test_int8_filter_bound_holds_for_cosine():
 
 
 def _l2aug_params(x, xn):
-    """vs_gemm_x1.hip l2aug_params: C = mean max|x| over the nonzero rows, nref
+    """vs_x1_planes.hip l2aug_params: C = mean max|x| over the nonzero rows, nref
     = the largest norm, m = max |nref - n_x| / (2 C max|x|) rounded up to 64
     (at least 64)."""
     mx = np.abs(x).max(axis=1).astype(np.float64)
@@ -236,7 +236,7 @@ def _quantize_i8_l2aug_queries(q, m, C):
 
 
 def test_int8_l2_augmented_bound_holds():
-    """L2 on the int8 plane (vs_gemm_x1.hip quantize_i8_l2aug_kernel, bound_key's
+    """L2 on the int8 plane (vs_x1_planes.hip quantize_i8_l2aug_kernel, vs_x1_verify.hip bound_key's
     l2aug branch, l2aug_map_kernel): the pass scores the augmented vectors
     x' = [x, e] (sum_j C e_j = (nref - n_x) / 2) and q' = [q, C ..] with the
     inner product's int8 arithmetic, A = -fl(fl(sum) fl(s_q s_x)) ~ n_x / 2 -
@@ -299,7 +299,7 @@ def _bf16(x):
 
 
 def test_bf16_l2_augmented_bound_holds():
-    """The bf16 plane's form of L2 as an inner product (vs_gemm_x1.hip
+    """The bf16 plane's form of L2 as an inner product (vs_x1_planes.hip
     bf16_plane_l2aug_kernel): x' = [bf16(x), 64 x bf16(E / 64)], E = (nref -
     n_x) / (2 Cb), q' = [bf16(q), Cb ..] with Cb a power of two (exact); the
     MFMA accumulates the products in fp32 (any order: gamma(ld + 1)); the list
@@ -348,7 +348,7 @@ def test_bf16_l2_augmented_bound_holds():
 
 
 def test_wide_threshold_below_the_floor_is_exact():
-    """The wide check may use any T' <= T (vs_gemm_x1.hip verify_wide_kernel):
+    """The wide check may use any T' <= T (vs_x1_verify.hip verify_wide_kernel):
     with a_M the M-th smallest approximate key, T' = min(T, a_M + 2.000001 B)
     keeps every row outside S at key >= T' and the M best-approximate rows in S
     (exact keys <= a_M + B), so the check passes whenever T' < T; whenever it
@@ -425,7 +425,7 @@ def _stream_lists(a, owner, P, L, order, cut_at=None, B=None, M=None, late=0):
     """Lane lists fed row by row in `order` (admission key < the list's last
     entry, as the kernel's), optionally with a query cut set after the first
     `cut_at` rows: cut = a_M(lists now) + 2.000001 B, and later rows are admitted
-    only below min(last, cut) (vs_gemm_x1.hip "Query cuts").  Returns the lists,
+    only below min(last, cut) (vs_x1_cuts.hip "Query cuts").  Returns the lists,
     the cut (inf without one) and the number of rows admitted after row
     `late` (= cut_at or the same point of the run without a cut)."""
     lists = [[] for _ in range(P)]
@@ -492,7 +492,7 @@ def test_query_cut_keeps_both_checks_and_drops_admissions():
 
 
 def _order_image(k):
-    """vs_gemm_x1.hip key_order: float order as unsigned order."""
+    """vs_x1_device.h key_order: float order as unsigned order."""
     u = np.asarray(k, np.float32).view(np.uint32).astype(np.uint64)
     return np.where(u & 0x80000000, (~u) & 0xFFFFFFFF, u | 0x80000000)
 

@@ -1,5 +1,5 @@
-"""GPU: the query cuts taken again after every replay (vs_gemm_x1.hip
-x1_replay_cut_kernel, x1_launch; env VS_X1_RECUT).
+"""GPU: the query cuts taken again after every replay (vs_x1_cuts.hip
+x1_replay_cut_kernel, vs_gemm_x1.hip x1_plan; env VS_X1_RECUT).
 
 The searches of test_gpu_dump.py: 4,096 queries (16 query tiles, 32 splits)
 over 300,000 x 128 rows with launches of 8 tiles (VS_X1_CHUNK_TILES=8): a list

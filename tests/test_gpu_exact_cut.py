@@ -1,4 +1,4 @@
-"""GPU: the exact-key cuts of the int8 inner-product pass (vs_gemm_x1.hip
+"""GPU: the exact-key cuts of the int8 inner-product pass (vs_x1_cuts.hip
 x1_ecut_kernel; env VS_X1_ECUT) and its quarter-length list
 launch (env VS_X1_QUARTER).
 

@@ -34,7 +34,7 @@ def vf():
 
 # Filter-and-verify planes: int8 (the first stage by default) and bf16; an L2
 # index's int8 plane holds the augmented rows (L2 as an inner product,
-# vs_gemm_x1.hip quantize_i8_l2aug_kernel).
+# vs_x1_planes.hip quantize_i8_l2aug_kernel).
 FILTER_CASES = [(L2, "bf16v"), (L2, "i8v"), (IP, "bf16v"), (IP, "i8v")]
 
 

@@ -207,7 +207,7 @@ def test_vectorised_checker_agrees_with_mismatches(metric):
 def _engine_keys(xb, xq, metric):
     """The filter engine's final keys restated in numpy: fp64 dot products
     rounded once, fp64-summed norms rounded once, L2 by faiss's BLAS formula in
-    fp32 (vs_gemm_x1.hip exact_key, vs_device.h l2_from_ip)."""
+    fp32 (vs_x1_device.h exact_key, vs_device.h l2_from_ip)."""
     ip = (xq.astype(np.float64) @ xb.astype(np.float64).T).astype(np.float32)
     if metric == IP:
         return ip

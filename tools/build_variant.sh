@@ -1,10 +1,14 @@
 #!/bin/bash
-# Builds an A/B variant of libvsearch.so with extra -D flags on vs_gemm_x1.hip:
+# Builds an A/B variant of libvsearch.so with extra -D flags on vs_gemm_x1.hip
+# (VS_X1_PROBE, VS_X1_STAMP, VS_X1_SCHED_I8, VS_X1_SEGDMA: the filter pass's
+# other units read none):
 #   tools/build_variant.sh <suffix> [-DNAME=VAL ...]  ->  vsearch/libvsearch_<suffix>.so
 #   X1_SRC=<file> tools/build_variant.sh <suffix> ...  (another vs_gemm_x1.hip, e.g.
-#   `git show HEAD~1:...` saved to a file, for before/after A/B)
+#   `git show HEAD~1:...` saved to a file, for before/after A/B; it must fit
+#   this tree's other units)
 # Select it at run time with VSEARCH_LIB=<that path> (tools/ab_x1.sh, x1_probe.sh).
-# Needs the default build's objects (make first).
+# Needs the default build's objects (make first): every other object of the
+# Makefile's list is linked as it is.
 set -e
 cd "$(dirname "$0")/../book-recommendation-engine_amd/csrc"
 sfx=$1; shift
@@ -14,6 +18,6 @@ mkdir -p build_$sfx
   -Rpass-analysis=kernel-resource-usage -x hip -c "$src" -o build_$sfx/vs_gemm_x1.o \
   2> build_$sfx/vs_gemm_x1.remarks
 python3 ../../tools/check_no_spill.py build_$sfx/vs_gemm_x1.remarks gemm_topk_x1 || [ -n "${ALLOW_SPILL:-}" ]  # stamp builds: bf16 kernels spill (diagnose int8 only)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../vsearch/libvsearch_$sfx.so \
-  build/vs_api.o build/vs_exact.o build/vs_gemm.o build_$sfx/vs_gemm_x1.o build/vs_gemv.o build/vs_skinny.o build/vs_support.o
+objs=$(make -s print-objs | sed "s#build/vs_gemm_x1\.o#build_$sfx/vs_gemm_x1.o#")
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../vsearch/libvsearch_$sfx.so $objs
 echo "built vsearch/libvsearch_$sfx.so"
