@@ -512,4 +512,47 @@ hipError_t launch_gemv_topk_rows(int KP, int mode, int nq, const void* X, int es
                                  const float* Q, int64_t ld, const int* list, int count,
                                  int nblocks, Partials part, hipStream_t st);
 
+// Range search (vs_range.hip; vs_api.hip vs_range_search).
+// The candidate passes: gemm_topk's loop with a threshold epilogue.  A row is
+// a candidate of query q iff row < ntotal and its GEMM key (IP: -score, L2: the
+// norm expansion) is <= thr[q] (nq_pad entries; NaN admits nothing).  fill =
+// false: cnt[q * nsplit + split] = the query's candidates among the split's
+// rows.  fill = true, with off = the exclusive scan of cnt (nq_pad * nsplit + 1
+// entries): the candidates' rows, ascending, at cand[off[q * nsplit + split] ..);
+// nothing is written outside a segment, and *err = 1 if a segment does not
+// come out as counted.
+hipError_t launch_gemm_range(bool fill, int mode, const void* X, const float* xaux, const void* Q,
+                             const float* qaux, int64_t ld, int esize, int ntotal, int nq_pad,
+                             int nsplit, const float* thr, int* cnt, const int64_t* off,
+                             int* cand, int* err, hipStream_t st);
+// out[0] = bits of the largest non-NaN norm of rows [0, n), out[1] = out[2] = 0
+// (the `stats` of launch_qbound with BoundArgs::rows_exact); part = scratch of
+// range_norm_max_parts() entries.
+int range_norm_max_parts();
+hipError_t launch_range_norm_max(const float* norms, int64_t n, unsigned* part, unsigned* out,
+                                 hipStream_t st);
+// thr[q] = radkey + bkey[q] rounded up for q < nq (NaN radkey: NaN; a bound
+// that is NaN: +inf), NaN for the padding queries [nq, nq_pad).
+hipError_t launch_range_thr(const double* bkey, int nq, int nq_pad, float radkey, float* thr,
+                            hipStream_t st);
+// off[0 .. n] = the exclusive scan of cnt[0 .. n) (off[n] = the total).
+hipError_t launch_range_scan(const int* cnt, int64_t n, int64_t* off, hipStream_t st);
+// Candidate c of query q (off[q * nsplit] <= c < off[(q + 1) * nsplit]):
+// ekey[c] = its exact key as a score (exact_key<mode>: distance, or inner
+// product), flag[c] = the key passes the radius strictly (L2 / L2D: key <
+// radius, IP: score > radius) and, with rbits, the row's selector bit is set.
+hipError_t launch_range_verify(int mode, const int* cand, int64_t total, const int64_t* off,
+                               int nsplit, int nq, const void* X, int xesize, const float* xn,
+                               const float* Q, const float* qn, int64_t ld, int ntotal,
+                               float radius, const uint32_t* rbits, float* ekey, uint8_t* flag,
+                               hipStream_t st);
+// hits[q] = the flags set among query q's candidates.
+hipError_t launch_range_hits(const uint8_t* flag, const int64_t* off, int nsplit, int nq,
+                             int* hits, hipStream_t st);
+// Stable compaction of every query's flagged candidates to D (score) and I
+// (row + id_base) at lims[q] (lims = the exclusive scan of hits).
+hipError_t launch_range_emit(const int* cand, const float* ekey, const uint8_t* flag,
+                             const int64_t* off, int nsplit, int nq, const int64_t* lims,
+                             int64_t id_base, float* D, int64_t* I, hipStream_t st);
+
 }  // namespace vs

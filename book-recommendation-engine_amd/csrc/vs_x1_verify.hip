@@ -595,6 +595,10 @@ __global__ __launch_bounds__(64) void qbound_kernel(const float* __restrict__ Q,
   double qh2, qr2, qn2;
   query_split_norms(Q + (int64_t)q * ld, ld, lane, qr2i8 ? qr2i8 + q : nullptr, qh2, qr2, qn2,
                     ba.aug_q2);
+  if (ba.rows_exact) {  // the fp32 GEMM multiplied q itself (as verify_rescore_kernel)
+    qh2 = qn2;
+    qr2 = 0.0;
+  }
   double b = bound_key(MODE, ba, qh2, qr2,
                                 MODE == MODE_L2 || MODE == MODE_L2D ? (double)qn[q] : qn2, stats);
   // the augmented L2 pass cuts its lists in the inner-product keys A, whose
@@ -617,6 +621,8 @@ hipError_t launch_qbound(int mode, const float* Q, int64_t ld, const float* qn, 
     VS_QB(MODE_L2);
   else if (mode == MODE_COS)
     VS_QB(MODE_COS);
+  else if (mode == MODE_L2D)  // the range search's small L2 calls (the extra norm term)
+    VS_QB(MODE_L2D);
   else
     return hipErrorInvalidValue;
 #undef VS_QB

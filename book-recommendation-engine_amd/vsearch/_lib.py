@@ -64,6 +64,12 @@ SIGNATURES = {
     "vs_selector_count": (_c_int, [_vp, _i64p]),
     "vs_selector_destroy": (_c_int, [_vp]),
     "vs_search_sel": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp]),
+    "vs_range_search": (_c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_float, _c_int, _vp,
+                                 ctypes.POINTER(_vp)]),
+    "vs_range_size": (_c_int, [_vp, _i64p, _i64p]),
+    "vs_range_candidates": (_c_int, [_vp, _i64p]),
+    "vs_range_copy": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _vp]),
+    "vs_range_destroy": (_c_int, [_vp]),
     "vs_reconstruct_n": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _vp]),
     "vs_remove_ids": (_c_int, [_vp, _vp, _c_i64, _i64p]),
     "vs_selfjoin": (

@@ -18,6 +18,9 @@ not vendored) that the reference reaches through LangChain's ``FAISS`` store:
   nearest rows among the selected labels, in place of the reference's
   search-``k * 2``-then-drop loops (candidate_builder.py:187-203,
   service.py:529-542,627-640)
+* ``index.range_search(x, thresh)`` — every row within a radius, in place of
+  the reference's thresholds applied after a k-bounded search
+  (graph_refresher/main.py:339-354, mcp_book_server.py:818-896)
 
 Argument checks mirror faiss's python wrapper (``assert d == self.d``,
 ``assert k > 0``); library failures raise ``RuntimeError`` subclasses.
@@ -449,6 +452,76 @@ class IndexFlat(Index):
                                        I.ctypes.data, _lib.RAW_ORDER if raw else 0, None),
                    "vs_search")
         return D, I
+
+    # queries per vs_range_search call (the C-ABI's limit); larger batches are
+    # searched in chunks and the parts concatenated
+    _RANGE_CHUNK = 65536
+
+    def _range_call(self, x, thresh, sel_handle):
+        """One vs_range_search call: (lims int64 (n+1), D, I) as numpy arrays."""
+        n = x.shape[0]
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.vs_range_search(self._h, sel_handle, x.ctypes.data, n,
+                                             ctypes.c_float(thresh), 0, None, ctypes.byref(h)),
+                   "vs_range_search")
+        try:
+            nq = ctypes.c_int64(0)
+            total = ctypes.c_int64(0)
+            _lib.check(self._lib.vs_range_size(h, ctypes.byref(nq), ctypes.byref(total)),
+                       "vs_range_size")
+            lims = np.empty(nq.value + 1, dtype=np.int64)
+            D = np.empty(total.value, dtype=np.float32)
+            I = np.empty(total.value, dtype=np.int64)
+            _lib.check(self._lib.vs_range_copy(h, lims.ctypes.data,
+                                               D.ctypes.data if total.value else None,
+                                               I.ctypes.data if total.value else None, 0, None),
+                       "vs_range_copy")
+        finally:
+            self._lib.vs_range_destroy(h)
+        return lims, D, I
+
+    def range_search(self, x, thresh, *, params=None):
+        """faiss Index.range_search: every row within the radius, as many as
+        there are.  Returns (lims uint64 (n+1), D float32, I int64): query i's
+        hits are D[lims[i]:lims[i+1]] / I[lims[i]:lims[i+1]], in ascending label
+        order (faiss leaves the order unspecified).
+
+        The comparison is faiss's strict one — L2: squared distance < thresh,
+        inner product: score > thresh — decided for every row by its exact key
+        (the key a search returns after rescoring), which is also what D holds.
+        ``params=SearchParameters(sel=...)`` restricts the hits to the selected
+        labels, as in ``search``."""
+        x = _as_f32_rows(x)
+        n, d = x.shape
+        assert d == self._d
+        thresh = float(thresh)
+        if n == 0:
+            return (np.zeros(1, dtype=np.uint64), np.empty(0, dtype=np.float32),
+                    np.empty(0, dtype=np.int64))
+        sel = getattr(params, "sel", None) if params is not None else None
+        handle, owned = self._resolve_selector(sel) if sel is not None else (None, False)
+        try:
+            sh = handle._h if handle is not None else None
+            step = self._RANGE_CHUNK
+            cuts = list(range(0, n, step)) + [n]
+            # the L2 key follows the call's size (fewer than 20 queries: faiss's
+            # sequential sum): a short tail borrows from the chunk before it
+            if len(cuts) > 2 and n - cuts[-2] < 20 < step // 2:
+                cuts[-2] -= 20
+            parts = [self._range_call(x[c0:c1], thresh, sh) for c0, c1 in zip(cuts, cuts[1:])]
+        finally:
+            if owned:
+                handle.close()
+        lims = np.zeros(n + 1, dtype=np.uint64)
+        base, q0 = 0, 0
+        for pl, _, _ in parts:
+            m = len(pl) - 1
+            lims[q0 + 1:q0 + m + 1] = (pl[1:] + base).astype(np.uint64)
+            base += int(pl[-1])
+            q0 += m
+        D = np.concatenate([p[1] for p in parts]) if len(parts) > 1 else parts[0][1]
+        I = np.concatenate([p[2] for p in parts]) if len(parts) > 1 else parts[0][2]
+        return lims, D, I
 
     def search_device(self, xq_ptr: int, n: int, k: int, D_ptr: int, I_ptr: int,
                       stream: int = 0, raw: bool = False, selector=None) -> None:

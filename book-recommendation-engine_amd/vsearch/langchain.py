@@ -514,6 +514,45 @@ class FAISS:
         return [d for d, _ in self.similarity_search_with_score(
             query, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
 
+    def similarity_search_within_score_by_vector(self, embedding: List[float],
+                                                 score_threshold: float,
+                                                 filter: Optional[Any] = None
+                                                 ) -> List[Tuple[Document, float]]:
+        """Every document within `score_threshold` of `embedding`, however many
+        there are, as (Document, score), best first (ties by label) — a range
+        search (``index.range_search``) instead of a k-bounded search cut at a
+        guessed k.  The comparison is faiss's strict one: distance <
+        score_threshold for an L2 index, score > score_threshold for an
+        inner-product index.  `filter` restricts the hits exactly, through the
+        store's selector (as ``exact_filter=True``).  Library-specific, like
+        ``upsert_texts``: LangChain's FAISS store has no counterpart."""
+        vector = np.array([embedding], dtype=np.float32)
+        if self._normalize_L2:
+            vfaiss.normalize_L2(vector)
+        params = None
+        if filter is not None:
+            params = vfaiss.SearchParameters(sel=self._filter_selector(filter))
+        _, scores, labels = self.index.range_search(vector, float(score_threshold), params=params)
+        scores = np.asarray(scores)
+        labels = np.asarray(labels)
+        key = -scores if self.index.metric_type == vfaiss.METRIC_INNER_PRODUCT else scores
+        docs = []
+        for j in np.lexsort((labels, key)):
+            _id = self.index_to_docstore_id[int(labels[j])]
+            doc = self.docstore.search(_id)
+            if not isinstance(doc, Document):
+                raise ValueError(f"Could not find document for id {_id}, got {doc}")
+            docs.append((doc, scores[j]))
+        return docs
+
+    def similarity_search_within_score(self, query: str, score_threshold: float,
+                                       filter: Optional[Any] = None
+                                       ) -> List[Tuple[Document, float]]:
+        """``similarity_search_within_score_by_vector`` of the embedded query
+        (library-specific)."""
+        return self.similarity_search_within_score_by_vector(self._embed_query(query),
+                                                             score_threshold, filter=filter)
+
     def similarity_search_batch_by_vector(self, embeddings, k: int = 4):
         """Batched variant (one engine call for many queries): list of
         [(Document, score)] per query, label -1 skipped."""

@@ -210,6 +210,44 @@ int vs_selector_destroy(vs_selector* sel);
 int vs_search_sel(vs_index* idx, const vs_selector* sel, const float* x, int64_t n, int64_t k,
                   float* D, int64_t* I, int flags, void* stream);
 
+/* ---- range search ----------------------------------------------------------
+ * faiss IndexFlat::range_search(n, x, radius, result[, params.sel]): every row
+ * within the radius, as many as there are — strict comparisons as faiss, L2:
+ * squared distance < radius, inner product: score > radius.  Replaces the
+ * reference's thresholds applied after a k-bounded search
+ * (src/graph_refresher/main.py:339-354 similarity_threshold,
+ * src/recommendation_api/mcp_book_server.py:818-896 min_similarity, LangChain's
+ * score_threshold), which cut "everything at least this similar" at a guessed k.
+ *
+ * A row is decided by its EXACT key alone (fp64 sum rounded once, the key the
+ * staged engine's rescoring returns: L2 calls with n < 20 as the direct sum of
+ * squares, n >= 20 as |q|^2 + |x|^2 - 2 q.x clamped at 0; bf16 indexes over the
+ * stored values and bf16-rounded queries), so the result does not depend on
+ * tiling or batch padding and is bit-identical from run to run.  D holds that
+ * key as a score (distance / inner product).  Each query's hits come in
+ * ascending label order.  A NaN radius and rows with NaN keys (tombstoned rows)
+ * match nothing.  A non-NULL selector restricts the hits to its rows (a stale
+ * one: VS_E_INVALID, as vs_search_sel).
+ *
+ * The result handle owns device buffers and outlives the index.  The call
+ * always synchronises `stream` (it reads two totals to size its buffers; on a
+ * capturing stream: VS_E_UNSUPPORTED).  n == 0 or an empty index: success, lims
+ * all 0.  n > 65536, or 2^31 or more candidates or hits: VS_E_UNSUPPORTED
+ * (callers chunk the queries).  flags: VS_IN_DEVICE. */
+typedef struct vs_range vs_range;
+int vs_range_search(vs_index* idx, const vs_selector* sel /* may be NULL */, const float* x,
+                    int64_t n, float radius, int flags, void* stream, vs_range** out);
+int vs_range_size(const vs_range* r, int64_t* nq, int64_t* total);
+/* The rows the candidate passes handed to the verification (>= total; the
+ * difference is the price of the preselection's bound).  Library-specific;
+ * tools/bench_range.py reports it. */
+int vs_range_candidates(const vs_range* r, int64_t* out);
+/* lims: nq + 1 int64 (lims[0] = 0, lims[nq] = total); D / I: total entries
+ * (query q's hits are [lims[q], lims[q + 1])).  VS_OUT_DEVICE: all three are
+ * device pointers on the index's device, the copy stream-ordered on `stream`. */
+int vs_range_copy(const vs_range* r, int64_t* lims, float* D, int64_t* I, int flags, void* stream);
+int vs_range_destroy(vs_range* r);
+
 /* faiss Index::reconstruct_n(i0, n, out) / reconstruct(i) — rows as added
  * (bf16 storage returns the stored bf16 value widened to float32).
  * Callers: store.index.reconstruct at candidate_builder.py:166-168, service.py:490-494. */
