@@ -555,4 +555,29 @@ hipError_t launch_range_emit(const int* cand, const float* ekey, const uint8_t* 
                              const int64_t* off, int nsplit, int nq, const int64_t* lims,
                              int64_t id_base, float* D, int64_t* I, hipStream_t st);
 
+// Profile searches (vs_profile.hip; vs_api.hip vs_search_excl / vs_mean_rows /
+// vs_search_profiles).
+// A class batch: dst row s = src row qmap[s] (rows of rowbytes, a multiple of
+// 16) and daux[s] = saux[qmap[s]] for s < cnt, zero rows / 0 for the padding
+// slots [cnt, nslot).  saux / daux may be null.
+hipError_t launch_excl_gather(const void* src, int64_t rowbytes, const float* saux,
+                              const int* qmap, int cnt, int nslot, void* dst, float* daux,
+                              hipStream_t st);
+// launch_sel_drop with one excluded set per query: slot s of Din / Iin
+// ([nq][k_in], labels = row + id_base, -1 empty) is query q = qmap[s] (null: s);
+// its entries whose row is not in rows[offs[q] .. offs[q + 1]) (ascending), in
+// order, are the first k_out entries of row q of Dout / Iout (padded with the
+// empty result of `mode`).
+hipError_t launch_excl_drop(int mode, const float* Din, const int64_t* Iin, int nq, int k_in,
+                            const int64_t* offs, const int64_t* rows, const int* qmap,
+                            int64_t id_base, float* Dout, int64_t* Iout, int k_out,
+                            hipStream_t st);
+// out[q][0 .. d) = the weighted mean of the rows rows[offs[q] .. offs[q + 1])
+// (rows in place, fp32 or bf16 of stride ld) with weights wts, divided by W[q]:
+// fp32, list order, no FMA, a correctly rounded division (the kernel's header).
+// Every segment holds at least one row; out has stride d.
+hipError_t launch_mean_rows(const void* X, int esize, int64_t ld, int d, const int64_t* offs,
+                            const int64_t* rows, const float* wts, const float* W, int64_t nq,
+                            float* out, hipStream_t st);
+
 }  // namespace vs

@@ -64,6 +64,10 @@ SIGNATURES = {
     "vs_selector_count": (_c_int, [_vp, _i64p]),
     "vs_selector_destroy": (_c_int, [_vp]),
     "vs_search_sel": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp]),
+    "vs_search_excl": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "vs_mean_rows": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_int, _vp]),
+    "vs_search_profiles": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
+                                    _vp, _c_int, _vp]),
     "vs_range_search": (_c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_float, _c_int, _vp,
                                  ctypes.POINTER(_vp)]),
     "vs_range_size": (_c_int, [_vp, _i64p, _i64p]),

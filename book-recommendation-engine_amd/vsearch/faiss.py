@@ -21,6 +21,11 @@ not vendored) that the reference reaches through LangChain's ``FAISS`` store:
 * ``index.range_search(x, thresh)`` — every row within a radius, in place of
   the reference's thresholds applied after a k-bounded search
   (graph_refresher/main.py:339-354, mcp_book_server.py:818-896)
+* ``index.search(x, k, exclude=...)``, ``index.mean_rows(profiles)`` and
+  ``index.search_profiles(profiles, k)`` — the reference's per-student
+  candidate path (reconstruct the rated books, weighted mean, search, drop the
+  books already read: candidate_builder.py:138-203) for many students in one
+  call, every query with its own exclusion list
 
 Argument checks mirror faiss's python wrapper (``assert d == self.d``,
 ``assert k > 0``); library failures raise ``RuntimeError`` subclasses.
@@ -57,6 +62,8 @@ __all__ = [
     "SearchParameters",
     "Selector",
     "selector_bitmap",
+    "exclusion_csr",
+    "profile_csr",
     "normalize_L2",
     "read_index",
     "write_index",
@@ -203,6 +210,61 @@ def selector_bitmap(sel, ntotal: int, id_base: int = 0) -> np.ndarray:
     labels = np.arange(int(id_base), int(id_base) + ntotal, dtype=np.int64)
     mask = _members(sel, labels) if ntotal else np.zeros(0, dtype=bool)
     return np.packbits(mask, bitorder="little")
+
+
+def exclusion_csr(exclude, n: int):
+    """Per-query label lists as a CSR: (offs int64 (n + 1), labels int64).
+
+    ``exclude`` is a sequence of n label sequences (any of them empty), or an
+    ``(offs, labels)`` pair already in that form; ``None`` is n empty lists."""
+    n = int(n)
+    if exclude is None:
+        return np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    # a pair of arrays whose first has n + 1 entries from 0 to len(second) is the
+    # CSR form (two label lists for n == 2 would have to look exactly like that)
+    if (isinstance(exclude, tuple) and len(exclude) == 2
+            and all(isinstance(e, np.ndarray) and e.ndim == 1 for e in exclude)
+            and exclude[0].size == n + 1 and exclude[0][0] == 0
+            and exclude[0][-1] == exclude[1].size):
+        offs = np.ascontiguousarray(exclude[0], dtype=np.int64)
+        labels = np.ascontiguousarray(exclude[1], dtype=np.int64).ravel()
+        if offs[0] != 0 or np.any(np.diff(offs) < 0) or offs[-1] != labels.size:
+            raise ValueError("exclude: offsets must rise from 0 to len(labels)")
+        return offs, labels
+    lists = [np.asarray(e if e is not None else (), dtype=np.int64).ravel() for e in exclude]
+    if len(lists) != n:
+        raise ValueError(f"exclude: expected {n} lists, got {len(lists)}")
+    offs = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        np.cumsum([e.size for e in lists], out=offs[1:])
+    labels = np.concatenate(lists) if n and offs[-1] else np.zeros(0, dtype=np.int64)
+    return offs, np.ascontiguousarray(labels, dtype=np.int64)
+
+
+def profile_csr(profiles):
+    """A sequence of ``(labels, weights)`` profiles as a CSR: (offs int64
+    (n + 1), labels int64, weights float32)."""
+    labs, wts = [], []
+    for p in profiles:
+        l, w = p
+        l = np.asarray(l, dtype=np.int64).ravel()
+        w = np.asarray(w, dtype=np.float32).ravel()
+        if l.size != w.size:
+            raise ValueError("profile: as many weights as labels")
+        labs.append(l)
+        wts.append(w)
+    n = len(labs)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        np.cumsum([l.size for l in labs], out=offs[1:])
+    labels = np.concatenate(labs) if n else np.zeros(0, dtype=np.int64)
+    weights = np.concatenate(wts) if n else np.zeros(0, dtype=np.float32)
+    return (offs, np.ascontiguousarray(labels, dtype=np.int64),
+            np.ascontiguousarray(weights, dtype=np.float32))
+
+
+def _ptr(a: np.ndarray):
+    return a.ctypes.data if a.size else None
 
 
 class SearchParameters:
@@ -410,8 +472,14 @@ class IndexFlat(Index):
         return self.selector(sel), True
 
     # -- queries -----------------------------------------------------------------------
-    def search(self, x, k, *, params=None, D=None, I=None, raw: bool = False):
+    def search(self, x, k, *, params=None, D=None, I=None, raw: bool = False, exclude=None):
         """faiss Index.search: returns (D float32 (n,k), I int64 (n,k)).
+
+        ``exclude`` gives every query its own list of labels to leave out: a
+        sequence of n label sequences, or an ``(offs, labels)`` CSR pair
+        (``exclusion_csr``).  The k nearest rows among the others come back
+        (fewer than k pad with label -1); labels the index does not hold are
+        ignored.  Not together with ``params.sel``.
 
         ``params=SearchParameters(sel=...)`` restricts the search to the selected
         labels (an IDSelector tree, built and freed in this call, or a
@@ -434,9 +502,20 @@ class IndexFlat(Index):
             I = np.empty((n, k), dtype=np.int64)
         else:
             assert I.shape == (n, k)
+        sel = getattr(params, "sel", None) if params is not None else None
+        if exclude is not None:
+            if sel is not None:
+                raise ValueError("search: pass exclude or params.sel, not both")
+            offs, labels = exclusion_csr(exclude, n)
+            if n == 0:
+                return D, I
+            _lib.check(self._lib.vs_search_excl(self._h, x.ctypes.data, n, k, offs.ctypes.data,
+                                                _ptr(labels), D.ctypes.data, I.ctypes.data,
+                                                _lib.RAW_ORDER if raw else 0, None),
+                       "vs_search_excl")
+            return D, I
         if n == 0:
             return D, I
-        sel = getattr(params, "sel", None) if params is not None else None
         if sel is not None:
             handle, owned = self._resolve_selector(sel)
             try:
@@ -451,6 +530,56 @@ class IndexFlat(Index):
         _lib.check(self._lib.vs_search(self._h, x.ctypes.data, n, k, D.ctypes.data,
                                        I.ctypes.data, _lib.RAW_ORDER if raw else 0, None),
                    "vs_search")
+        return D, I
+
+    def mean_rows(self, profiles) -> np.ndarray:
+        """The weighted means of stored rows, computed on the device: profile
+        i is ``(labels, weights)`` and row i of the result (float32 (n, d)) is
+        ``np.sum([reconstruct(l) * w ...], axis=0) / sum(weights)`` bit for bit
+        (fp32, list order; the weights as float32, their sum taken in double
+        and rounded once).  A label the index does not hold, an empty profile
+        or a zero weight sum raise RuntimeError."""
+        offs, labels, weights = profile_csr(profiles)
+        n = offs.size - 1
+        out = np.empty((n, self._d), dtype=np.float32)
+        if n:
+            _lib.check(self._lib.vs_mean_rows(self._h, offs.ctypes.data, _ptr(labels),
+                                              _ptr(weights), n, out.ctypes.data, 0, None),
+                       "vs_mean_rows")
+        return out
+
+    def mean_rows_device(self, profiles, out_ptr: int, stream: int = 0) -> None:
+        """``mean_rows`` into a device buffer of n * d float32 on this index's
+        device, stream-ordered on ``stream``."""
+        offs, labels, weights = profile_csr(profiles)
+        n = offs.size - 1
+        if n:
+            _lib.check(self._lib.vs_mean_rows(self._h, offs.ctypes.data, _ptr(labels),
+                                              _ptr(weights), n, ctypes.c_void_p(out_ptr),
+                                              _lib.OUT_DEVICE, ctypes.c_void_p(stream)),
+                       "vs_mean_rows")
+
+    def search_profiles(self, profiles, k, *, exclude=None, exclude_profile: bool = True,
+                        raw: bool = False):
+        """``search(mean_rows(profiles), k, exclude=...)`` in one call, the
+        means staying on the device: returns (D, I) as ``search``.  With
+        ``exclude_profile`` every profile's own labels are excluded from its
+        result too (the rated books are the mean's nearest rows)."""
+        offs, labels, weights = profile_csr(profiles)
+        n = offs.size - 1
+        k = int(k)
+        assert k > 0
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        if n == 0:
+            return D, I
+        eoffs, elabels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+        _lib.check(self._lib.vs_search_profiles(
+            self._h, offs.ctypes.data, _ptr(labels), _ptr(weights), n, k,
+            eoffs.ctypes.data if eoffs is not None else None,
+            _ptr(elabels) if elabels is not None else None, 1 if exclude_profile else 0,
+            D.ctypes.data, I.ctypes.data, _lib.RAW_ORDER if raw else 0, None),
+            "vs_search_profiles")
         return D, I
 
     # queries per vs_range_search call (the C-ABI's limit); larger batches are

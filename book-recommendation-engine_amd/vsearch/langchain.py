@@ -23,6 +23,11 @@ types and error behaviour:
   format plus a JSON docstore sidecar (``index.docstore.json``; LangChain's
   ``index.pkl`` needs LangChain's classes to unpickle and is not read);
   ``load_local`` still demands ``allow_dangerous_deserialization=True``.
+* ``recommend_for_profiles`` (library-specific) — the per-student candidate
+  path of candidate_builder.py:138-203 (weighted mean of the rated books'
+  embeddings, search, drop the books already read) for many students in one
+  device call; ``similarity_search_with_score_by_vector(..., exclude_ids=)``
+  for one query.
 """
 
 from __future__ import annotations
@@ -202,6 +207,9 @@ class FAISS:
         self._keymap: Dict[Any, List[str]] = {}
         # exact_filter selectors by the filter's JSON; dropped by every add / delete / merge
         self._sel_cache: Dict[str, Any] = {}
+        # (field, metadata[field] -> labels), built once per store generation
+        # (the labels move with every delete): dropped with _sel_cache
+        self._keylabels: Optional[Tuple[str, Dict[Any, List[int]]]] = None
         if (self.distance_strategy != DistanceStrategy.EUCLIDEAN_DISTANCE
                 and self._normalize_L2):
             warnings.warn(
@@ -244,6 +252,7 @@ class FAISS:
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
         self._sel_cache.clear()
+        self._keylabels = None
         self.index.add(vector)
         self.docstore.add({id_: doc for id_, doc in zip(ids, documents)})
         starting_len = len(self.index_to_docstore_id)
@@ -343,6 +352,7 @@ class FAISS:
         reversed_index = {id_: idx for idx, id_ in self.index_to_docstore_id.items()}
         index_to_delete = {reversed_index[id_] for id_ in ids}
         self._sel_cache.clear()
+        self._keylabels = None
         self.index.remove_ids(np.fromiter(index_to_delete, dtype=np.int64))
         if self._keymap_field is not None:
             for id_ in ids:
@@ -368,6 +378,7 @@ class FAISS:
             raise ValueError("Cannot merge with this type of docstore")
         index_offset = len(self.index_to_docstore_id)
         self._sel_cache.clear()
+        self._keylabels = None
         if target.index.ntotal:
             self.index.add(target.index.reconstruct_n(0, target.index.ntotal))
         full_info = []
@@ -466,11 +477,23 @@ class FAISS:
                                                **kwargs: Any) -> List[Tuple[Document, float]]:
         """``exact_filter=True``: the k nearest documents among those that pass
         `filter` (exactly min(k, matches) of them; `fetch_k` is ignored), by a
-        selector search, instead of filtering the `fetch_k` nearest on the host."""
+        selector search, instead of filtering the `fetch_k` nearest on the host.
+
+        ``exclude_ids=[...]`` (docstore ids; unknown ones are ignored): those
+        documents are left out of the search itself, so k others come back
+        (library-specific; not together with ``exact_filter``)."""
         vector = np.array([embedding], dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
-        if exact_filter and filter is not None:
+        exclude_ids = kwargs.get("exclude_ids")
+        if exclude_ids is not None:
+            if exact_filter and filter is not None:
+                raise ValueError("exclude_ids and exact_filter cannot be combined")
+            wanted = set(exclude_ids)
+            drop = [i for i, id_ in self.index_to_docstore_id.items() if id_ in wanted]
+            scores, indices = self.index.search(vector, k if filter is None else fetch_k,
+                                                exclude=[drop])
+        elif exact_filter and filter is not None:
             scores, indices = self.index.search(
                 vector, k, params=vfaiss.SearchParameters(sel=self._filter_selector(filter)))
             filter = None  # every label returned passes it
@@ -569,6 +592,90 @@ class FAISS:
                 doc = self.docstore.search(self.index_to_docstore_id[int(i)])
                 row.append((doc, scores[qi][j]))
             out.append(row)
+        return out
+
+    # -- profile searches -------------------------------------------------------------------
+    def _key_labels(self, field: str) -> Dict[Any, List[int]]:
+        """metadata[field] -> labels holding it, ascending.  Built once per
+        store generation from ``_key_index`` (every add / delete drops it)."""
+        if self._keylabels is None or self._keylabels[0] != field:
+            label_of = {id_: i for i, id_ in self.index_to_docstore_id.items()}
+            table = {value: sorted(label_of[id_] for id_ in ids)
+                     for value, ids in self._key_index(field).items()}
+            self._keylabels = (field, table)
+        return self._keylabels[1]
+
+    def _docs_of_row(self, scores, labels) -> List[Tuple[Document, float]]:
+        out = []
+        for s, i in zip(scores, labels):
+            if i == -1:
+                continue
+            _id = self.index_to_docstore_id[int(i)]
+            doc = self.docstore.search(_id)
+            if not isinstance(doc, Document):
+                raise ValueError(f"Could not find document for id {_id}, got {doc}")
+            out.append((doc, s))
+        return out
+
+    def profile_requests(self, profiles, exclude=None, key: str = "book_id"):
+        """What ``index.search_profiles`` takes for `profiles`: (kept, rows,
+        lists).  kept = the positions of the profiles with at least one key in
+        the store; rows[j] = (labels, weights) of profile kept[j], a key's
+        first row standing for it as the reference's scan does
+        (candidate_builder.py:159-163); lists[j] = every label of its rated and
+        excluded keys."""
+        table = self._key_labels(key)
+        kept, rows, lists = [], [], []
+        for p, profile in enumerate(profiles):
+            labels, weights, drop = [], [], []
+            for value, weight in profile:
+                found = table.get(value)
+                if found:
+                    labels.append(found[0])
+                    weights.append(weight)
+                    drop.extend(found)
+            if not labels:
+                continue
+            if exclude is not None:
+                for value in exclude[p]:
+                    drop.extend(table.get(value, ()))
+            kept.append(p)
+            rows.append((labels, weights))
+            lists.append(drop)
+        return kept, rows, lists
+
+    def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
+                               key: str = "book_id") -> List[List[Tuple[Document, float]]]:
+        """The reference's per-student candidate path
+        (candidate_builder.py:138-203) for many students in one device call.
+        Each profile is a list of ``(metadata[key] value, weight)`` — a
+        student's rated books with their ``RATING_WEIGHTS``; ``exclude[i]``
+        holds further key values profile i must not get back (the books
+        already read).  The query of a profile is the weighted mean of its
+        books' stored embeddings, and its result the k nearest documents that
+        are neither rated nor excluded: exactly min(k, allowed) ``(Document,
+        score)`` pairs, where the reference's search of ``k * 2`` rows returns
+        fewer when most of them were read.  A profile none of whose keys are
+        in the store gets ``[]``, as the reference returns, and takes no part
+        in the device call.  Library-specific: LangChain's store has no
+        counterpart."""
+        profiles = list(profiles)
+        if exclude is not None:
+            exclude = list(exclude)
+            _len_check_if_sized(profiles, exclude, "profiles", "exclude")
+        out: List[List[Tuple[Document, float]]] = [[] for _ in profiles]
+        kept, rows, lists = self.profile_requests(profiles, exclude, key)
+        if not kept:
+            return out
+        if self._normalize_L2:  # the store normalises every query it searches
+            vec = self.index.mean_rows(rows)
+            vfaiss.normalize_L2(vec)
+            scores, labels = self.index.search(vec, k, exclude=lists)
+        else:
+            scores, labels = self.index.search_profiles(rows, k, exclude=lists,
+                                                        exclude_profile=False)
+        for j, p in enumerate(kept):
+            out[p] = self._docs_of_row(scores[j], labels[j])
         return out
 
     def _select_relevance_score_fn(self) -> Callable[[float], float]:

@@ -19,6 +19,10 @@ HBM and serves the same vector-store calls to any number of clients:
 * Writers (``add_texts`` / ``upsert_texts`` / ``delete`` / ``save_local``) take the
   store exclusively; readers share it (readers-writer lock), the same ordering
   faiss gives (concurrent ``search`` allowed, ``add`` exclusive).
+* Per-student requests coalesce too: a search may carry one exclusion list per
+  row (op ``search`` with ``exclude``), and ``recommend_for_profiles`` takes a
+  student's weighted-mean query and the books they have read into the same
+  stacked batch as everyone else's (``index.search(x, k, exclude=...)``).
 * ``RemoteFAISS(address, authkey)`` is the client: the LangChain ``FAISS`` read /
   write surface the reference's call sites use, plus ``.index.ntotal/.d/.search``.
 * Access: the HMAC auth key has no default (the caller supplies a secret);
@@ -107,10 +111,11 @@ class _RWLock:
 
 
 class _Pending:
-    __slots__ = ("vec", "k", "done", "D", "I", "err")
+    __slots__ = ("vec", "k", "exclude", "done", "D", "I", "err")
 
-    def __init__(self, vec: np.ndarray, k: int):
-        self.vec, self.k = vec, k
+    def __init__(self, vec: np.ndarray, k: int, exclude: Optional[Sequence] = None):
+        # exclude: one label list per row of vec (None: nothing excluded)
+        self.vec, self.k, self.exclude = vec, k, exclude
         self.done = threading.Event()
         self.D = self.I = self.err = None
 
@@ -121,7 +126,9 @@ class _Coalescer:
     One dispatcher thread: it takes everything queued (up to max_batch rows),
     groups by k, runs one ``index.search`` per group, and hands each caller its
     rows.  Callers hold the service's read lock while they wait.  A lone
-    request runs at once (no added wait)."""
+    request runs at once (no added wait).  Requests may carry one exclusion
+    list per row (``index.search(x, k, exclude=...)``): they stack with the
+    others of their k, the rows of requests without lists excluding nothing."""
 
     def __init__(self, service: "IndexService", max_batch: int):
         self._svc = service
@@ -134,8 +141,11 @@ class _Coalescer:
         self._thread = threading.Thread(target=self._run, name="vsearch-coalescer", daemon=True)
         self._thread.start()
 
-    def submit(self, vec: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        p = _Pending(vec, k)
+    def submit(self, vec: np.ndarray, k: int,
+               exclude: Optional[Sequence] = None) -> Tuple[np.ndarray, np.ndarray]:
+        if exclude is not None and len(exclude) != vec.shape[0]:
+            raise ValueError("exclude: one label list per query row")
+        p = _Pending(vec, k, exclude)
         with self._cv:
             self._queue.append(p)
             self._cv.notify()
@@ -172,7 +182,14 @@ class _Coalescer:
                     x = np.concatenate([p.vec for p in ps]) if len(ps) > 1 else ps[0].vec
                     # every submitter holds the read lock while it waits, so no
                     # writer can run during this call
-                    D, I = self._svc.store.index.search(x, k)
+                    if any(p.exclude is not None for p in ps):
+                        lists: List[Sequence[int]] = []
+                        for p in ps:
+                            lists.extend(p.exclude if p.exclude is not None
+                                         else [()] * p.vec.shape[0])
+                        D, I = self._svc.store.index.search(x, k, exclude=lists)
+                    else:
+                        D, I = self._svc.store.index.search(x, k)
                     self.batches += 1
                     self.rows += x.shape[0]
                     r = 0
@@ -311,7 +328,8 @@ class IndexService:
                                        "distance_strategy": st.distance_strategy.value}), b""
         if op == "search":  # faiss-level: (n, d) -> D (n, k) f32, I (n, k) i64
             x = self._vectors(h, payload)
-            D, I = self._read(self._coalescer.submit, x, int(h["k"]))
+            # "exclude": one list of labels per row, left out of that row's result
+            D, I = self._read(self._coalescer.submit, x, int(h["k"]), h.get("exclude"))
             return {"shape": list(D.shape)}, (np.ascontiguousarray(D, "<f4").tobytes()
                                               + np.ascontiguousarray(I, "<i8").tobytes())
         if op == "similarity_search_with_score":
@@ -320,6 +338,8 @@ class IndexService:
             else:
                 vec = self._vectors(h, payload)
             return {"results": self._search_docs(vec, h)}, b""
+        if op == "recommend_for_profiles":
+            return {"results": self._recommend(h)}, b""
         if op == "embed_query":
             return {"vector": [float(v) for v in st._embed_query(h["query"])]}, b""
         if op == "add_texts":
@@ -343,6 +363,31 @@ class IndexService:
             v = self._read(st.index.reconstruct, int(h["key"]))
             return {"shape": [int(v.shape[0])]}, np.ascontiguousarray(v, "<f4").tobytes()
         raise ValueError(f"unknown op {op!r}")
+
+    def _recommend(self, h: dict) -> List[list]:
+        """FAISS.recommend_for_profiles with the search coalesced: the means
+        are taken on the device at once, the search stacks with whatever other
+        requests of the same k are waiting, each row under its own exclusions."""
+        st = self.store
+        profiles = [[(v, float(w)) for v, w in p] for p in h["profiles"]]
+        exclude = h.get("exclude")
+        if exclude is not None and len(exclude) != len(profiles):
+            raise ValueError("profiles and exclude expected to be equal length")
+        out: List[list] = [[] for _ in profiles]
+        self._lock.acquire_read()  # held from the label lookup to the docstore lookup
+        try:
+            kept, rows, lists = st.profile_requests(profiles, exclude, h.get("key", "book_id"))
+            if kept:
+                vec = st.index.mean_rows(rows)
+                if st._normalize_L2:
+                    from . import faiss as vfaiss
+                    vfaiss.normalize_L2(vec)
+                D, I = self._coalescer.submit(vec, int(h.get("k", 4)), lists)
+                for j, p in enumerate(kept):
+                    out[p] = [[d.to_json(), float(s)] for d, s in st._docs_of_row(D[j], I[j])]
+        finally:
+            self._lock.release_read()
+        return out
 
     def _search_docs(self, vec: np.ndarray, h: dict) -> List[list]:
         """FAISS.similarity_search_with_score_by_vector with the engine call coalesced
@@ -400,10 +445,14 @@ class _RemoteIndex:
     def metric_type(self) -> int:
         return int(self._c._call({"op": "info"})[0]["metric_type"])
 
-    def search(self, x, k: int):
+    def search(self, x, k: int, *, exclude=None):
+        """``exclude``: one sequence of labels per query row, left out of that
+        row's result (``IndexFlat.search(x, k, exclude=...)``)."""
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
-        h, p = self._c._call({"op": "search", "k": int(k), "shape": list(x.shape)},
-                             x.astype("<f4").tobytes())
+        header = {"op": "search", "k": int(k), "shape": list(x.shape)}
+        if exclude is not None:
+            header["exclude"] = [[int(l) for l in e] for e in exclude]
+        h, p = self._c._call(header, x.astype("<f4").tobytes())
         n, kk = h["shape"]
         D = np.frombuffer(p, dtype="<f4", count=n * kk).reshape(n, kk).astype(np.float32)
         I = np.frombuffer(p[n * kk * 4:], dtype="<i8", count=n * kk).reshape(n, kk).astype(np.int64)
@@ -477,6 +526,16 @@ class RemoteFAISS:
                           exact_filter: bool = False, **kwargs) -> List[Document]:
         return [d for d, _ in self.similarity_search_with_score(
             query, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
+
+    def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
+                               key: str = "book_id") -> List[List[Tuple[Document, np.float32]]]:
+        """``FAISS.recommend_for_profiles`` on the server; concurrent callers
+        share one engine batch."""
+        header = {"op": "recommend_for_profiles", "k": int(k), "key": key,
+                  "profiles": [[[v, float(w)] for v, w in p] for p in profiles],
+                  "exclude": None if exclude is None else [list(e) for e in exclude]}
+        res = self._call(header)[0]["results"]
+        return [[(Document.from_json(d), np.float32(s)) for d, s in row] for row in res]
 
     def get_by_ids(self, ids: Sequence[str]) -> List[Document]:
         return [Document.from_json(d) for d in self._call({"op": "get_by_ids",

@@ -210,6 +210,56 @@ int vs_selector_destroy(vs_selector* sel);
 int vs_search_sel(vs_index* idx, const vs_selector* sel, const float* x, int64_t n, int64_t k,
                   float* D, int64_t* I, int flags, void* stream);
 
+/* ---- profile searches ------------------------------------------------------
+ * The reference's per-student candidate path (reconstruct the embeddings of
+ * the books a student rated, take their weighted mean, search k * 2, drop the
+ * books already read: src/recommendation_api/candidate_builder.py:138-203,
+ * service.py:490-542, 627-640) for many students in one call: every query has
+ * its own exclusion list, and the queries can be built on the device from
+ * stored rows.
+ *
+ * vs_search with one exclusion list per query.  excl_offs: n + 1 HOST int64
+ * offsets, non-decreasing from 0; query q excludes the labels
+ * excl_labels[excl_offs[q] .. excl_offs[q + 1]) (HOST int64).  Duplicates, -1
+ * and labels that are not live labels of the index are ignored, as
+ * vs_remove_ids ignores them.  Outputs, padding (fewer than k allowed rows pad
+ * with (+FLT_MAX | -FLT_MAX, -1)), tie rules (over the allowed rows only),
+ * VS_OUT_DEVICE, VS_RAW_ORDER, any k and the stream contract are vs_search's;
+ * VS_IN_DEVICE applies to x only; the L2 formula follows the whole call's n.
+ * excl_offs == NULL or all lists empty: vs_search itself.
+ * Queries are grouped by the size m of their list (0; at most 16, 64, 256,
+ * 1024; larger), and a group whose longest list holds c rows runs the engine
+ * for k2 = min(need + c, live rows) raw entries (need = 2k - 1 for inner
+ * product under faiss's tie rule, k otherwise) before its excluded rows are
+ * dropped; groups the engine would serve with the same list length run as one.
+ * So a query costs what its own group's longest list costs, not the call's:
+ * k2 > 1024 leaves the staged engine for the paged one (k2 / 64 passes over
+ * the rows), and k2 > INT_MAX/2 is VS_E_INVALID. */
+int vs_search_excl(vs_index* idx, const float* x, int64_t n, int64_t k, const int64_t* excl_offs,
+                   const int64_t* excl_labels, float* D, int64_t* I, int flags, void* stream);
+/* n weighted means of stored rows: profile q is the labels
+ * labels[offs[q] .. offs[q + 1]) with weights weights[...] (HOST CSR; offs:
+ * n + 1 int64 from 0).  out: n * d float32, host or (VS_OUT_DEVICE) device.
+ * Computed on the device in fp32, in list order, without FMA:
+ *   acc = x[l0] * w0;  acc = fl(acc + fl(x[li] * wi));  out = fl(acc / W)
+ * W = the weights summed in double in list order, rounded once to fp32; the
+ * division is correctly rounded — numpy's np.sum([emb_i * w_i], axis=0) /
+ * total_weight (candidate_builder.py:170-176) bit for bit for float32 rows.
+ * bf16 indexes use the stored value widened to fp32, as vs_reconstruct_n
+ * returns it.  VS_E_INVALID: a label that is not a live label (faiss
+ * reconstruct throws), an empty profile, W zero or not finite. */
+int vs_mean_rows(vs_index* idx, const int64_t* offs, const int64_t* labels, const float* weights,
+                 int64_t n, float* out, int flags, void* stream);
+/* Both in one call: the means of vs_mean_rows (kept on the device) searched as
+ * vs_search_excl searches them.  excl_offs may be NULL; exclude_profile != 0
+ * adds every profile's own labels to its exclusion list (the rated books are
+ * the mean's nearest rows; the reference's already_read set holds them).
+ * flags: VS_OUT_DEVICE, VS_RAW_ORDER. */
+int vs_search_profiles(vs_index* idx, const int64_t* offs, const int64_t* labels,
+                       const float* weights, int64_t n, int64_t k, const int64_t* excl_offs,
+                       const int64_t* excl_labels, int exclude_profile, float* D, int64_t* I,
+                       int flags, void* stream);
+
 /* ---- range search ----------------------------------------------------------
  * faiss IndexFlat::range_search(n, x, radius, result[, params.sel]): every row
  * within the radius, as many as there are — strict comparisons as faiss, L2:
