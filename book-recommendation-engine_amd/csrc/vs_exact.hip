@@ -2,7 +2,7 @@
 // the queries no proof settles (the staged engine's last resort).
 //
 // The filter stages prove their candidate sets; the last
-// stage (vs_api.hip run_gemm_rescored) takes the fp32 MFMA GEMM's top-KF and
+// stage (vs_engines.hip run_gemm_rescored) takes the fp32 MFMA GEMM's top-KF and
 // proves them with the fp32 GEMM's own error bound.  A query whose k-th best
 // row has more than KF - k rows inside that bound (dense near-ties: copies of
 // a row spaced below the fp32 GEMM's rounding) cannot be proven from any
@@ -16,7 +16,7 @@
 //
 // With a floor per query (fkey / fid: the paged engine's previous page) it is
 // the exact-key form of a page: the staged engine's last stage past 64
-// candidates (vs_api.hip run_paged, gathered) pages each query's order of exact
+// candidates (vs_engines.hip run_paged, gathered) pages each query's order of exact
 // keys 64 entries at a time.
 //
 // Layout: one workgroup per block of rows (4 waves, each wave 4 rows at a

@@ -40,7 +40,7 @@ namespace vs {
 // FLOOR (KP = 64 only, every metric): the lists admit only entries that come
 // strictly after the query's floor (fkey[q], fid[q]) in (key, row) order — page
 // p + 1 of a query's lexicographic order starts after page p's last entry
-// (vs_api.hip run_paged: any k, and faiss's inner-product tie rule, which reads
+// (vs_engines.hip run_paged: any k, and faiss's inner-product tie rule, which reads
 // up to 2k - 1 entries).  Every page of a search runs this instantiation (page 1
 // with the floor (-inf, -1)), so a row's key is bit-identical in all pages.
 template <int KP, int MODE, typename T, bool FLOOR = false>

@@ -1473,7 +1473,7 @@ static int x1_first_den(int el, bool ecut) {
 // The launch plan of a pass: which launches run over which parts of every
 // workgroup's tiles, of which kind, and what runs between them.  Host only and
 // pure (the knobs above are its only other inputs): x1_launch executes it,
-// x1_pass_dumps asks it whether a pass has dump launches (vs_api.hip allocates
+// x1_pass_dumps asks it whether a pass has dump launches (vs_engines.hip allocates
 // the dump slots and cuts by that), and vs_x1_plan shows it to CPU tests.
 enum X1Kind : int { kX1List = 0, kX1Hybrid = 1, kX1Dump32 = 2, kX1Dump16 = 3 };
 // what follows a launch, in this order (a bit mask)

@@ -28,7 +28,7 @@ __device__ __forceinline__ void widen_chunk(const uint4 v, float (&f)[16 / sizeo
 }
 
 // FLOOR: query q's list admits only rows strictly after (fkey[q], fid[q]) in
-// (key, row) order (page p + 1 of the paged engine, vs_api.hip run_paged; a
+// (key, row) order (page p + 1 of the paged engine, vs_engines.hip run_paged; a
 // query with nothing left to page gets the floor (+inf, INT_MAX) and an empty
 // list); `run` (optional device flag): nothing to do when *run == 0.
 template <int NQ, int KP, int MODE, typename T, bool FLOOR = false>

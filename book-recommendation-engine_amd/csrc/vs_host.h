@@ -1,0 +1,408 @@
+// vs_host.h — what the host-only units of the C-ABI share (vs_api*.hip,
+// vs_engines.hip, vs_storage.hip, vs_runtime.hip): the handle types, the
+// per-call helpers and the declarations of what crosses those units.  The
+// kernel units include vs_internal.h alone.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <shared_mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/vsearch.h"
+#include "vs_internal.h"
+
+// bf16-first searches between int8 probes: the first gap, doubling to the last.
+constexpr int kI8FirstBackoff = 8;
+constexpr int kI8MaxBackoff = 64;
+
+struct vs_index {
+  int d = 0;
+  int metric = VS_METRIC_L2;
+  int dtype = VS_DTYPE_F32;
+  int device = 0;
+  int esize = 4;         // bytes per stored element (4 fp32, 2 bf16)
+  int64_t ld = 0;        // row stride in elements, a multiple of 64 (zero padding)
+  int64_t ntotal = 0;
+  int64_t capacity = 0;  // rows allocated (multiple of kRowPad, >= ntotal + 256)
+  int64_t id_base = 0;
+  // bumped by whatever moves rows or changes labels (add, remove_ids, reset, a
+  // tombstone pack, set_id_base): a selector built before is stale
+  uint64_t gen = 0;
+  char* codes = nullptr;   // [capacity][ld] elements
+  int64_t rowbytes() const { return ld * esize; }
+  char* row(int64_t r) const { return codes + r * rowbytes(); }
+  float* norms = nullptr;  // [capacity] squared L2 norms
+  // fp32 indexes: the filter planes the filter passes multiply ([capacity][ld]
+  // each, kept in step with the rows by add / remove_ids / growth) and
+  // |x - plane(x)|^2 per row for the bound: [FILTER_I8] int8 codes + a per-row
+  // scale (inner-product indexes), [FILTER_BF16] bf16 (round-to-nearest-even)
+  // copies.  bf16 indexes use the exact bf16 engine, no plane.
+  bool plane_on[2] = {false, false};
+  char* fplane[2] = {nullptr, nullptr};
+  float* rn2[2] = {nullptr, nullptr};
+  float* fscale = nullptr;  // int8 plane: s = max|x| / 127 per row
+  // per plane: max |x|^2, max |x - plane(x)|^2, max of their ratio over the
+  // rows (the bound's index maxima; grown by add, recomputed by remove_ids)
+  unsigned* bstats[2] = {nullptr, nullptr};
+  // L2 indexes: both planes hold augmented rows x' = [x, e_1 .. e_m] whose
+  // inner product with q' = [q, C .. C] ranks rows as the L2 key does
+  // (launch_quantize_i8_l2aug, launch_bf16_plane_l2aug); the parameters are
+  // set by the first add (aug_m = 0 before), anorm / anorm_b = |x'|^2 per row
+  // (the planes' bound maxima use them)
+  int aug_m = 0;
+  vs::L2Aug aug;
+  float* anorm = nullptr;
+  float* anorm_b = nullptr;
+  // Tombstones (indexes without filter planes, e.g. bf16 storage): removed
+  // rows stay in place, NaN-filled (no kernel admits them), until a pack; faiss
+  // labels are positions among the live rows (searches map their rows through
+  // the sorted dead list, launch_label_map).  ntotal counts the rows in place.
+  std::string notice;  // the last plane loss (vs_notice), empty if none
+  std::vector<int64_t> dead;
+  int64_t* ddead = nullptr;  // device copy of `dead`
+  int64_t ddead_cap = 0;
+  int64_t live() const { return ntotal - (int64_t)dead.size(); }
+  // removals fill rows with NaN in place (labels mapped at search time) instead
+  // of compacting at once: bf16 indexes (C5: 154 GB of rows cannot move at every
+  // removal; an int8 plane of theirs has its factors set to NaN with them) and
+  // indexes without planes
+  bool tombstones() const { return esize == 2 || (!plane_on[0] && !plane_on[1]); }
+  bool l2aug() const { return metric == VS_METRIC_L2 && esize == 4; }
+  int64_t planebytes(int p) const {
+    if (!l2aug()) return ld * vs::filter_bytes(p);
+    return (p == vs::FILTER_I8 ? ld + aug_m : ld + vs::kAugBf16) * vs::filter_bytes(p);
+  }
+  // Adaptive plane order: the int8 stage pays off while it settles most
+  // queries; on data where it hands most of them to bf16 (clustered
+  // embeddings) the searches go to bf16 directly, re-probing int8 with an
+  // exponential backoff.  Device counters [i8 queries, handed to bf16], read
+  // through a pinned mirror when the copy's event has completed (no host wait).
+  struct Adaptive {
+    std::mutex mu;
+    unsigned long long* dcount = nullptr;
+    unsigned long long* hmirror = nullptr;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    unsigned long long seen_q = 0, seen_h = 0;
+    double ema = 0.0;
+    bool have = false;
+    int skip_left = 0, backoff = kI8FirstBackoff;
+  } ad;
+  int engine = VS_ENGINE_AUTO;
+  std::shared_mutex mu;
+  // Completion marks of the calls that read this index's storage on the
+  // device: one event per stream a search / self-join / device reconstruct ran
+  // on, recorded after its last launch.  Writers that move or free the storage
+  // (growth, remove_ids, reset, destroy) wait for these marks only — not for
+  // the whole device, where other indexes' searches may be running (faiss's
+  // contract: a writer excludes the readers of its own index).
+  std::mutex rd_mu;
+  std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
+  hipStream_t wst = nullptr;  // the index's own (non-blocking) writer stream
+};
+
+// A selector of one index (vs_selector_create): the selected rows in place as
+// a bitmap and as an ascending list (vs_select.hip), valid while the index's
+// generation is the one it was built at.
+struct vs_selector {
+  vs_index* idx = nullptr;
+  int device = 0;
+  uint64_t gen = 0;
+  int64_t count = 0;         // selected live rows
+  uint32_t* rbits = nullptr;  // [whole compaction blocks over ntotal] row bitmap
+  int* list = nullptr;        // [count rounded up to kBN] ascending rows, padded
+};
+
+// Route (b) of vs_search_sel serves selections that leave at most this many
+// live rows out (a fixed condition of the route, not a tuned threshold).
+constexpr int64_t kSelMaxExcluded = 256;
+
+// A range search's result (vs_range_search): device buffers of its own, so it
+// outlives the index.
+struct vs_range {
+  int device = 0;
+  int64_t nq = 0;
+  int64_t total = 0;
+  int64_t ncand = 0;        // rows the candidate passes handed to the verification
+  int64_t* lims = nullptr;  // [nq + 1]
+  float* D = nullptr;       // [total]
+  int64_t* I = nullptr;     // [total]
+};
+
+namespace vs {
+namespace host {
+
+// The calling thread's last error (vs_last_error); returns `code`.
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* what);
+
+#define VS_HIP(expr, what)                    \
+  do {                                        \
+    hipError_t e_ = (expr);                   \
+    if (e_ != hipSuccess) return hip_fail(e_, what); \
+  } while (0)
+
+// VS_HIP with the message "<what><tail>" (what: the entry point's name, a
+// run-time value in the helpers several entry points share; composed only on
+// failure).
+#define VS_HIPW(expr, what, tail)                                                   \
+  do {                                                                              \
+    hipError_t e_ = (expr);                                                         \
+    if (e_ != hipSuccess) return hip_fail(e_, (std::string(what) + (tail)).c_str()); \
+  } while (0)
+
+// Selects the index's device for the duration of a call, restoring the caller's.
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+// Records a reader mark of `idx` on `st` when it leaves scope (after the
+// caller's last launch on st; also on an error return).
+struct ReaderMark {
+  vs_index* idx;
+  hipStream_t st;
+  ReaderMark(vs_index* i, hipStream_t s) : idx(i), st(s) {}
+  ~ReaderMark();
+};
+
+// Waits (host) until every reader mark of `idx` has completed.  Called with
+// the index's writer lock held, so no new reader can start meanwhile.
+hipError_t wait_readers(vs_index* idx);
+
+// The index's writer stream (created on first use): non-blocking, so it never
+// serialises with the legacy null stream's users, and of the greatest
+// priority, which gives it a hardware queue of its own — streams of one
+// priority share the process's few hardware queues (GPU_MAX_HW_QUEUES), and a
+// shared queue would run the writer behind another stream's search queue.
+hipError_t writer_stream(vs_index* idx, hipStream_t* out);
+
+// Per-call scratch: bump allocation from cached chunks, returned at scope end.
+struct Scratch {
+  static constexpr size_t kAlign = 256;
+  hipStream_t st;
+  std::vector<ScratchChunk> chunks;
+  char* cur = nullptr;
+  size_t left = 0;
+  explicit Scratch(hipStream_t s) : st(s) {}
+  hipError_t alloc(void** p, size_t bytes) {
+    *p = nullptr;
+    if (bytes == 0) return hipSuccess;
+    bytes = (bytes + kAlign - 1) & ~(kAlign - 1);
+    if (bytes > left) {
+      ScratchChunk c;
+      hipError_t e = scratch_chunk_get(bytes, st, &c);
+      if (e != hipSuccess) return e;
+      chunks.push_back(c);
+      cur = (char*)c.p;
+      left = c.size;
+    }
+    *p = cur;
+    cur += bytes;
+    left -= bytes;
+    return hipSuccess;
+  }
+  ~Scratch() {
+    for (auto& c : chunks) scratch_chunk_put(c, st);
+  }
+};
+
+// Filter-and-verify statistics, counted on the device (no host sync in a
+// search): [0] queries, [1] flagged by the first check (given to the wide
+// check), [2] flagged by both (redone by the exact engine), [3] handed to a
+// second filter stage, [4] wide-set entries, [5] of them rescored (the rest
+// reuse the first check's keys), [6] rows stored by dump launches (one
+// (row, raw sum) slot each), [7] lane lists out of dump slots.  One buffer per device.
+constexpr int kStatSlots = 9;  // [8]: queries ranked by the exact-key stream
+unsigned long long* device_stats(int dev);
+
+// Kernel timer (measurement hook for bench.py; see vs_timer_* in vsearch.h).
+struct KernelTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipStream_t st;
+  const char* name = nullptr;
+  int dispatches = 1;  // kernel launches between the two events
+  bool aux = false;
+  double share = 1.0;  // of a filter pass's tiles (X1SpanTimer)
+  // name == nullptr: untimed (the filter engine's exact redo, which is not the
+  // kernel the roofline is quoted on)
+  // names_kernel: this span names the search's dominant kernel (vs_timer_kernel);
+  // false for an extra span over several kernels (the whole filter pass)
+  KernelTimer(hipStream_t s, const char* nm, bool names_kernel = true);
+  void stop();
+};
+
+// The filter pass's per-launch spans: dump launches (and every launch of a
+// pass without dumps) under the pass's timer name, the list launch of a pass
+// with dumps under "<name>_list" (bench.py: the roofline is the dominant
+// kernel's own time; the cut and replay kernels between launches are in no
+// span).
+struct X1SpanTimer : X1Timing {
+  const char* name;
+  const char* list_name;
+  KernelTimer* cur = nullptr;
+  X1SpanTimer(const char* n, const char* ln) : name(n), list_name(ln) {}
+  void begin(hipStream_t st, bool dominant, double share) override {
+    cur = new KernelTimer(st, dominant ? name : list_name);
+    cur->share = share;
+  }
+  void end(hipStream_t) override {
+    if (!cur) return;
+    cur->stop();
+    delete cur;
+    cur = nullptr;
+  }
+  ~X1SpanTimer() override { end(nullptr); }
+};
+
+inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+inline int kp_for(int64_t k) {
+  return k <= 8      ? 8
+         : k <= 16   ? 16
+         : k <= 32   ? 32
+         : k <= 64   ? 64
+         : k <= 128  ? 128
+         : k <= 256  ? 256
+         : k <= 512  ? 512
+                     : 1024;
+}
+
+// What a search computes, shared by every engine.
+struct SearchArgs {
+  int mode = MODE_IP;
+  const float* qbuf = nullptr;   // [nq_pad][ld] fp32 query rows (zero padded)
+  const void* qb16 = nullptr;    // bf16 copy of the queries (bf16 indexes)
+  const float* qaux = nullptr;   // |q|^2 (L2) or 1/|q| (COS), nq_pad entries
+  const float* xaux = nullptr;   // per-row norms (L2) or 1/|x| (COS)
+  int nq = 0, nq_pad = 0, k = 0;
+  int64_t self0 = -1;            // self-join: query q is row self0 + q
+  float min_score = 0.0f;
+  int raw = 0;                   // VS_RAW_ORDER
+  bool l2_direct = false;        // faiss's sequential branch (the call's nq < 20)
+  // the call waits for its results anyway (host outputs): a small batch may
+  // read its device-side count after the first stage and skip the empty rest
+  bool host_wait = false;
+  float* D = nullptr;
+  int64_t* I = nullptr;
+};
+
+// ---- vs_storage.hip ---------------------------------------------------------
+void planes_for(vs_index* idx);
+void reset_l2aug(vs_index* idx);
+int derive_plane(vs_index* idx, int64_t r0, int64_t n, hipStream_t st, bool appended = false);
+int ensure_capacity(vs_index* idx, int64_t rows, hipStream_t st);
+void free_storage(vs_index* idx);
+int make_room(vs_index* idx, int64_t n, hipStream_t st);
+int compact_rows(vs_index* idx, const std::vector<int64_t>& rm, hipStream_t st);
+int pack_dead(vs_index* idx);
+int pack_den();
+int64_t row_of_label(const vs_index* idx, int64_t l);
+
+// ---- vs_engines.hip ---------------------------------------------------------
+int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engine);
+
+// Database splits of an exact GEMM launch over `ntiles` row tiles and `nqt`
+// query tiles (at most 512: one chunk of queries): ~2 workgroups per CU on 256
+// CUs, never more splits than tiles.
+inline int gemm_nsplit(int ntiles, int nqt) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (512 + nqt - 1) / nqt));
+}
+
+// ---- vs_api.hip: what the search entry points share -------------------------
+// The argument checks of a search, in the order every entry point makes them:
+// the index, the selector (sel_ok: false where a required one is null), n
+// (null: the caller checks its own count), k, then the buffers (bufs_ok; a
+// call of no queries needs none).  An entry point with checks of its own
+// before its buffers' (vs_search_excl's offsets) passes true and checks them
+// after those.  Messages are "<what>: ...".
+int check_search_args(const char* what, const vs_index* idx, const int64_t* n, int64_t k,
+                      bool bufs_ok = true, bool sel_ok = true);
+
+// A call's results on the device: the caller's buffers under VS_OUT_DEVICE,
+// else scratch that finish() copies to them before it waits for the stream.
+// I == nullptr: a call with one output (vs_mean_rows).
+struct HostOut {
+  float* D = nullptr;  // where the kernels write
+  int64_t* I = nullptr;
+  float* hD = nullptr;  // the caller's buffers
+  int64_t* hI = nullptr;
+  size_t count = 0;  // entries of each
+  bool out_dev = false;
+  int begin(const char* what, Scratch& scr, float* D_, int64_t* I_, size_t count_, int flags);
+  // last_error: a call with device outputs reports the thread's pending HIP
+  // error (vs_selfjoin never has: false)
+  int finish(const char* what, hipStream_t st, bool last_error = true);
+};
+
+// The staged queries of a call: fp32 rows of stride ld, zero padded to whole
+// query tiles, |q|^2 of every row (L2) and, for bf16 indexes, the rounded copy.
+struct QueryStage {
+  float* qbuf = nullptr;
+  float* qaux = nullptr;
+  uint16_t* qb16 = nullptr;
+};
+// Buffers for chunks of at most `cmax` queries.
+int stage_alloc(const char* what, const vs_index* idx, int64_t cmax, Scratch& scr, QueryStage* qs);
+// Stages the nc queries at x (host, or device under VS_IN_DEVICE) and fills
+// the SearchArgs fields that describe them: mode, qbuf, qb16, qaux, xaux, nq,
+// nq_pad.
+int stage_chunk(const char* what, const vs_index* idx, const QueryStage& qs, const float* x,
+                int64_t nc, int flags, hipStream_t st, SearchArgs* sa);
+
+// A search over n staged queries: the outputs (HostOut), the answer of an
+// index without rows to search (`empty`), else the queries in chunks of 65536
+// so that scratch stays bounded for any n — run(sa, c0) ranks the chunk that
+// starts at query c0 into sa.D / sa.I — and the rows found mapped to faiss
+// labels.  The caller holds the reader lock, the device and a reader mark on
+// `st`; `scr` is the call's scratch.
+template <class Run>
+int search_staged(const char* what, vs_index* idx, const float* x, int64_t n, int64_t k, float* D,
+                  int64_t* I, int flags, Scratch& scr, hipStream_t st, bool empty, Run run) {
+  HostOut out;
+  int rc = out.begin(what, scr, D, I, (size_t)n * k, flags);
+  if (rc) return rc;
+  if (empty) {
+    const int mode = idx->metric == VS_METRIC_L2 ? MODE_L2 : MODE_IP;
+    VS_HIPW(launch_fill_empty(mode, out.D, out.I, n * k, st), what, ": fill");
+    return out.finish(what, st);
+  }
+  const int64_t chunk = 65536;
+  QueryStage qs;
+  rc = stage_alloc(what, idx, std::min(n, chunk), scr, &qs);
+  if (rc) return rc;
+  for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+    SearchArgs sa;
+    rc = stage_chunk(what, idx, qs, x + c0 * idx->d, std::min(chunk, n - c0), flags, st, &sa);
+    if (rc) return rc;
+    sa.k = (int)k;
+    sa.raw = (flags & VS_RAW_ORDER) ? 1 : 0;
+    sa.l2_direct = n < kBlasThreshold;  // faiss decides on the whole call's nq
+    sa.host_wait = !out.out_dev;
+    sa.D = out.D + c0 * k;
+    sa.I = out.I + c0 * k;
+    rc = run(sa, c0);
+    if (rc) return rc;
+  }
+  // tombstoned rows never enter a list; the rows found become faiss labels
+  if (!idx->dead.empty())
+    VS_HIPW(launch_label_map(out.I, n * k, idx->ddead, (int64_t)idx->dead.size(), idx->id_base, st),
+            what, ": labels");
+  return out.finish(what, st);
+}
+
+}  // namespace host
+}  // namespace vs

@@ -1,5 +1,5 @@
 // Internal declarations shared by the kernel units (vs_*.hip: device code +
-// launchers) and vs_api.hip (the C-ABI).  Nothing here is part of the public ABI.
+// launchers) and the host units (vs_host.h).  Nothing here is part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -111,7 +111,7 @@ inline int filter_bytes(int filter) { return filter == FILTER_I8 ? 1 : 2; }
 __host__ __device__ inline int64_t plane_offset(int64_t row, int64_t byte, int64_t ldb) {
   return ((row >> 8) * (ldb >> 6) + (byte >> 6)) * 16384 + (row & 255) * 64 + (byte & 63);
 }
-// Per-launch timing hook of the filter pass (vs_api.hip): x1_launch brackets
+// Per-launch timing hook of the filter pass (vs_host.h X1SpanTimer): x1_launch brackets
 // every pass launch with begin/end; `dominant` is false for the list launch of
 // a pass that dumps (its spans are named apart from the dump launches').
 struct X1Timing {
@@ -333,7 +333,7 @@ bool select_heads_applies(const Partials& part, int L, int KF);
 hipError_t launch_select_heads(Partials part, int nq, int KF, float* Dk, int64_t* Ik,
                                hipStream_t st, const int* qcount = nullptr);
 
-// Scratch chunks (vs_api.hip): device memory of at least `bytes` whose previous
+// Scratch chunks (vs_runtime.hip): device memory of at least `bytes` whose previous
 // use the taker's stream `st` waits for; put records the chunk's last use on
 // `st` and keeps it for the next taker.  scratch_trim frees the idle chunks of
 // the current device (synchronising it).
@@ -408,7 +408,7 @@ struct ExactStreamArgs {
 int exact_stream_nq(int64_t ld);
 hipError_t launch_exact_stream(int KP, int mode, const ExactStreamArgs& a, Partials part,
                                hipStream_t st);
-// The paged exact engine (vs_support.hip, "paged exact engine"; vs_api.hip
+// The paged exact engine (vs_support.hip, "paged exact engine"; vs_engines.hip
 // run_paged).  Dacc/Iacc [n][KA]: the pages side by side (scores, local rows).
 // page_init: member/active flags (every q < n, or gl[0 .. *gc) of zeroed rows)
 // and the first page's floor (-inf, -1) for fkey/fid[0 .. nfloor).
@@ -473,7 +473,7 @@ hipError_t launch_gather_kept(const void* X, const float* norms, int64_t rowbyte
                               int64_t n, const int64_t* removed, int64_t nrem, void* tmp,
                               float* tmp_norms, hipStream_t st);
 
-// Selector searches (vs_select.hip; vs_api.hip vs_selector_create / vs_search_sel).
+// Selector searches (vs_select.hip; vs_api_select.hip vs_selector_create / vs_search_sel).
 // A selector is a bitmap over the rows in place (word r >> 5, bit r & 31) and
 // the ascending list of the selected rows.
 // Rows per compaction block: 256 words of 32 rows.
@@ -512,7 +512,7 @@ hipError_t launch_gemv_topk_rows(int KP, int mode, int nq, const void* X, int es
                                  const float* Q, int64_t ld, const int* list, int count,
                                  int nblocks, Partials part, hipStream_t st);
 
-// Range search (vs_range.hip; vs_api.hip vs_range_search).
+// Range search (vs_range.hip; vs_api_range.hip vs_range_search).
 // The candidate passes: gemm_topk's loop with a threshold epilogue.  A row is
 // a candidate of query q iff row < ntotal and its GEMM key (IP: -score, L2: the
 // norm expansion) is <= thr[q] (nq_pad entries; NaN admits nothing).  fill =
@@ -555,7 +555,7 @@ hipError_t launch_range_emit(const int* cand, const float* ekey, const uint8_t* 
                              const int64_t* off, int nsplit, int nq, const int64_t* lims,
                              int64_t id_base, float* D, int64_t* I, hipStream_t st);
 
-// Profile searches (vs_profile.hip; vs_api.hip vs_search_excl / vs_mean_rows /
+// Profile searches (vs_profile.hip; vs_api_profile.hip vs_search_excl / vs_mean_rows /
 // vs_search_profiles).
 // A class batch: dst row s = src row qmap[s] (rows of rowbytes, a multiple of
 // 16) and daux[s] = saux[qmap[s]] for s < cnt, zero rows / 0 for the padding

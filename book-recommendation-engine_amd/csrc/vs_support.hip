@@ -361,7 +361,7 @@ hipError_t launch_merge_parts(int mode, const float* Dp, const int64_t* Ip, int 
 }
 
 // ---------------------------------------------------------------------------
-// The paged exact engine (vs_api.hip run_paged): any k, every metric.  A
+// The paged exact engine (vs_engines.hip run_paged): any k, every metric.  A
 // query's answer is read off its lexicographic (key, row) order in pages of 64
 // entries, page p + 1 computed by the FLOOR form of the exact kernels (entries
 // strictly after page p's last one).  The pages of a window of n queries land

@@ -12,7 +12,7 @@ ties included:
     lexicographically best (-score, label) pairs of the whole corpus
     (oracle/flat.py faiss_order), so each shard returns its RAW best
     m = 2k-1 pairs (VS_RAW_ORDER, no tie rule applied; any k: the shard's
-    paged search, vs_api.hip run_paged) and the merge (vs_merge_topk, any
+    paged search, vs_engines.hip run_paged) and the merge (vs_merge_topk, any
     k_in) applies the rule once to the union of those lists.
 The exchange is B*m*12 bytes per rank: latency-bound, not link-bound.
 

@@ -61,7 +61,7 @@ extern "C" {
 /* The entries one exact page holds (register lists of 64).  Not a limit on k:
  * searches and self-joins that need more — k > 64, raw k > 64, faiss's
  * inner-product tie rule at k > 32 — read further pages of 64, each after the
- * previous page's last (key, label) (vs_api.hip run_paged), as faiss-cpu's
+ * previous page's last (key, label) (vs_engines.hip run_paged), as faiss-cpu's
  * IndexFlat::search answers any k. */
 #define VS_MAX_K 64
 

@@ -102,7 +102,7 @@ def _strict(D, I, ref, metric, xb, xq):
 def test_refreshed_cuts_are_exact_and_dump_fewer_rows(lib, uniform, indexes, monkeypatch, engine,
                                                       metric, k, tiles):
     """Inner product k = 28 (64 candidates) and the bf16 plane take 64 splits
-    of 19 tiles instead of 32 of 37 (vs_api.hip: twice the lists), which
+    of 19 tiles instead of 32 of 37 (vs_engines.hip: twice the lists), which
     8-tile launches cut into 3: a split pass, one dump launch, no launch left
     for a refreshed cut to act on (measured: 3,788,717 rows dumped either way
     at k = 28).  Those two cases run 4-tile launches, which give them the

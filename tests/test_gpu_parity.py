@@ -49,7 +49,7 @@ def _rand(n, d, seed, kind="normal"):
 
 def _staged(metric, nq, k, engine="auto"):
     """Whether a search of an fp32 index is answered by the staged
-    filter-and-verify engine (vs_api.hip run_topk: more than kSkinnyMaxQ = 32
+    filter-and-verify engine (vs_engines.hip run_topk: more than kSkinnyMaxQ = 32
     queries and a candidate count x1_list_len(need) > 0, need = 2k - 1 for IP)."""
     need = 2 * k - 1 if metric == IP else k
     return engine != "fp32" and nq > 32 and need + 8 <= 64
@@ -121,7 +121,7 @@ def test_empty_index(vf, metric):
 def test_ties_match_faiss_heap(vf, metric, k):
     """Tie-heavy integer data: labels must equal the C faiss-heap restatement
     exactly.  Inner product with k > 32 reads up to 2k - 1 = 127 entries: the
-    two-page search (vs_api.hip run_wide_k; nq = 1 on the GEMV, 7 and 40 on the
+    two-page search (vs_engines.hip run_paged; nq = 1 on the GEMV, 7 and 40 on the
     fp32 MFMA GEMM; service.py:529-531 asks for k = 60)."""
     xb = _rand(600, 3, 12, "int")
     for nq in (1, 7, 40):
@@ -711,7 +711,7 @@ def test_filter_every_query_falls_back(vf):
 
 
 def test_filter_redo_runs_in_slot_windows(vf):
-    """More flagged queries than one slot window of the exact redo (vs_api.hip
+    """More flagged queries than one slot window of the exact redo (vs_engines.hip
     run_gemm_rescored: lists capped at ~1 GB, here 11,136 slots at k = 20):
     every window is searched and rescored, queries of the second window included."""
     from vsearch import _lib

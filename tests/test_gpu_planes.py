@@ -1,7 +1,7 @@
 """GPU: the filter planes an fp32 index keeps, and what happens without them.
 
 * A memory shortage while the storage grows drops the bf16 plane, then both
-  (vs_api.hip ensure_capacity): the index says so (vs_notice, stderr) and
+  (vs_storage.hip ensure_capacity): the index says so (vs_notice, stderr) and
   `filter_planes` reports what is left; searches stay exact (VS_TEST_PLANE_OOM
   fails the plane allocations as a full HBM would; a process of its own, the
   hook is read once).

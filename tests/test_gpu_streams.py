@@ -1,7 +1,7 @@
 """GPU: concurrent device-resident searches on two streams of one index.
 
-Per-call scratch comes from a chunk cache shared by every stream (vs_api.hip
-Scratch / scratch_chunk_get): a chunk carries the event of its last use and a
+Per-call scratch comes from a chunk cache shared by every stream (vs_host.h
+Scratch, vs_runtime.hip scratch_chunk_get): a chunk carries the event of its last use and a
 taker on another stream waits for it on the device.  Two host threads, each on
 its own non-blocking stream, search the same index with different query sets
 over and over (the filter engine: int8 -> bf16 -> fp32 stages, many scratch
@@ -63,7 +63,7 @@ def test_two_streams_share_scratch_chunks():
 
 
 def test_writer_of_one_index_does_not_drain_another():
-    """Writers wait for their own index's readers only (vs_api.hip ReaderMark /
+    """Writers wait for their own index's readers only (vs_runtime.hip ReaderMark /
     wait_readers): remove_ids on a small index A returns while a queue of long
     searches of index B is still running on another stream, and both results
     stay exact.  (Storage growth frees the old buffers with hipFree; the time
@@ -134,7 +134,7 @@ def test_writer_of_one_index_does_not_drain_another():
 
 def test_tail_wait_keeps_device_results(monkeypatch):
     """Device-output searches read their first stage's leftover count and
-    enqueue the later stages only when queries remain (vs_api.hip
+    enqueue the later stages only when queries remain (vs_engines.hip
     tail_wait_on).  With queries beside 200 near-copies of their own direction
     (the int8 checks hand them on: the later stages run) and without (nothing
     left: the search ends after its first stage), the lists equal those of

@@ -2,7 +2,7 @@
 IndexFlat::search answers it (the live tool's k is the agent's,
 /root/reference/src/recommendation_api/mcp_book_server.py:115,142; LangChain
 passes fetch_k straight to index.search under a filter).  These searches run
-the paged exact engine (vs_api.hip run_paged): the exact fp32 / bf16 kernels
+the paged exact engine (vs_engines.hip run_paged): the exact fp32 / bf16 kernels
 page through each query's lexicographic (key, row) order 64 entries at a time.
 
 Acceptance: the fp32 contract of the north star (labels equal except ties

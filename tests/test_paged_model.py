@@ -1,5 +1,5 @@
 """CPU model of the paged exact engine's stopping rule (vs_support.hip
-page_step_kernel / page_finish, vs_api.hip run_paged): a query's
+page_step_kernel / page_finish, vs_engines.hip run_paged): a query's
 lexicographic (key, label) order is read in pages of 64, and the next page is
 fetched only while the page came back full and the answer needs more — fewer
 than k entries so far, or (faiss's inner-product rule) the k-th key's run of
