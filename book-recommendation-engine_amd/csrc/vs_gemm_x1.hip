@@ -3,8 +3,9 @@
 // lists.
 //
 // Every fp32 index keeps, beside its fp32 rows, a "filter plane" copy of every
-// row ([capacity][ld], row-major) and the squared norm of each row's residual
-// x - plane(x).  Two planes exist (vs_internal.h, Filter):
+// row (tile-major: the 64-B step s of the 256 rows of tile t is one contiguous
+// 16-KB block, plane_offset in vs_internal.h) and the squared norm of each
+// row's residual x - plane(x).  Two planes exist (vs_internal.h, Filter):
 //   int8 (default): code = rint(x / s) with one scale s = max|x| / 127 per row;
 //     the kernel multiplies codes on v_mfma_i32_32x32x32_i8 (exact int32 sums,
 //     twice the bf16 MFMA rate, 64 elements per 64-B step) and scales the sum
@@ -59,7 +60,8 @@
 // passes somewhere): about a sixth of the int8 pass (profiles/r04a/x1_probes.txt:
 // 3.45 ms per dispatch with the candidate work, 2.86 ms with the epilogue's
 // per-block test alone).  A dump costs one 8-B store per candidate row on the
-// lanes that pass.
+// lanes that pass, and the scan that finds the row: the scan is what is paid
+// for (the stores add nothing measurable).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -72,7 +74,10 @@
 // Diagnostic builds only (tools/x1_probe.sh; wrong results by design): a mask
 // of ablations — 1 no LDS-DMA, 2 no fragment reads, 4 no mid-step barrier,
 // 8 no epilogue, 16 no database pieces, 32 no query pieces, 64 no vmcnt wait in
-// the loop, 128 the epilogue's per-block test alone (no block ever passes).
+// the loop, 128 the epilogue's per-block test alone (no block ever passes),
+// 256 the dump branch in full (pass test, masks, count exchange, running
+// counts) without its stores (the launch leaves dcount as it found it, so the
+// replay reads no slot that was never written).
 #ifndef VS_X1_PROBE
 #define VS_X1_PROBE 0
 #endif
@@ -90,7 +95,10 @@ namespace vs {
 #endif
 constexpr int kStampSeg = 9;  // + inside the epilogue: reject, factor loads, keys/inserts
 constexpr int kStampCnt = 3;  // epilogue counts: factor loads, blocks inserting, inserts
-constexpr int kStampN = 2 * (kStampSeg + kStampCnt) + 2;
+// + the 16x16x64 dump launches' events (rows that take a slot) per lane and
+// launch, as a histogram of 0 .. 15+ [the pass's first dump launch | the rest]
+constexpr int kStampHist = 16;
+constexpr int kStampN = 2 * (kStampSeg + kStampCnt) + 2 + 2 * kStampHist;
 __device__ unsigned long long g_x1_stamps[kStampN];
 
 namespace {
@@ -772,11 +780,13 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         // Dump launch: every row of a block that passed whose sum clears the
         // limit (int8: above the launch's integer threshold; bf16: -sum below
         // the limit) goes to the lane list's
-        // next slot as (row, raw sum): one 8-B store per candidate row (the
-        // stores queue behind the DMA pieces like everything in the vector
-        // memory path: a whole block's 16 sums took five stores and ~4 % of a
-        // C3 step, profiles/r04f/stamp_c3_dump.txt).  A list past its dR slots
-        // counts on (the replay fails its query).
+        // next slot as (row, raw sum): one 8-B store per candidate row (a
+        // whole block's 16 sums took five stores and ~4 % of a C3 step,
+        // profiles/r04f/stamp_c3_dump.txt; the single stores cost nothing
+        // that can be measured: with them suppressed, VS_X1_PROBE=256, a C3
+        // dump launch takes as long, profiles/r10gate — the branch's cost is
+        // its VALU work).  A list past its dR slots counts on (the replay
+        // fails its query).
         // (a block, not an early return: one exit keeps the step loop's
         // branch to the epilogue a single compare)
         if (__ballot(pass != 0) != 0) {  // uniform: rare
@@ -809,7 +819,8 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
                   // slot-major (slot c of every list together): the replay's
                   // threads, one per list, read their c-th slots coalesced
                   const int64_t slot = (int64_t)c * ((int64_t)nqt * kT * P) + (int64_t)gq[qb] * P + pl;
-                  *(i32x2*)(dslot + slot * 2) = i32x2{row, sum};
+                  if constexpr (!(VS_X1_P(256) && DUMP)) *(i32x2*)(dslot + slot * 2) = i32x2{row, sum};
+                  else asm volatile("" ::"v"(slot), "v"(row), "v"(sum));
                 }
               }
             }
@@ -956,6 +967,15 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     // block the pair exchange their candidate counts (rows that take a slot
     // only), the lower lane stores first and both advance the count by the sum.
     // The control flow around the exchange is wave-uniform.
+    // What the branch costs is its scan, not its stores (profiles/r10gate: a
+    // C3 dump launch with the stores suppressed takes as long, one with no
+    // block ever passing 0.1-0.6 ms less), and every wave of the workgroup
+    // waits for the slowest at the next barrier: a query block that passed
+    // drops each 16-row block with one maximum and one compare before any
+    // per-row mask, and the count exchange stays out of the LDS pipe.
+#if VS_X1_STAMP
+    int nev = 0;  // the lane's events of this launch
+#endif
     auto epilogue16 = [&](int t) {
       if constexpr (S16) {
         const bool plain = self0 < 0 && !qrow && (t + 1) * kT <= ntotal;
@@ -989,6 +1009,12 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
             int* const dst = dslot + ((int64_t)gq[qb] * P + pl) * 2;
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
+              // most 16-row blocks of a query block that passed hold no
+              // candidate: one maximum and one compare (the ballot) drops them
+              // before the per-row masks
+              const int m4 = max(max(acc16[b][qb][0], acc16[b][qb][1]),
+                                 max(acc16[b][qb][2], acc16[b][qb][3]));
+              if (__ballot(m4 > Tq[qb]) == 0) continue;  // uniform
               uint32_t cm = 0;
 #pragma unroll
               for (int e = 0; e < 4; ++e) cm |= (uint32_t)(acc16[b][qb][e] > Tq[qb]) << e;
@@ -1003,14 +1029,28 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
               }
               if (__ballot(cm != 0) == 0) continue;  // uniform
               const int n = __popc(cm);
-              const int np = __shfl_xor(n, 32);  // the partner's count (every lane active)
+              // the partner's count (every lane active): v_permlane32_swap
+              // puts the lower lanes' n into the upper lanes of sw[0] and the
+              // upper lanes' n into the lower lanes of sw[1] — one VALU
+              // instruction, where a shuffle is a trip through the LDS pipe
+              // (ds_bpermute) and a wait for it
+              const auto sw = __builtin_amdgcn_permlane32_swap(n, n, false, false);
+              const int np = (int)(lane < 32 ? sw[1] : sw[0]);
               int c = dc[qb] + (lane >= 32 ? np : 0);
               dc[qb] += n + np;  // counts on past dR (the replay fails the query)
+#if VS_X1_STAMP
+              nev += min(n, max(dR - c, 0));
+#endif
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 if (cm & (1u << e)) {
-                  // slot-major, as in the 32x32 form
-                  if (c < dR) *(i32x2*)(dst + (int64_t)c * nl * 2) = i32x2{row0 + e, acc16[b][qb][e]};
+                  if constexpr (VS_X1_P(256)) {
+                    if (c < dR) asm volatile("" ::"v"(dst + (int64_t)c * nl * 2), "v"(row0 + e),
+                                             "v"(acc16[b][qb][e]));
+                  } else {
+                    // slot-major, as in the 32x32 form
+                    if (c < dR) *(i32x2*)(dst + (int64_t)c * nl * 2) = i32x2{row0 + e, acc16[b][qb][e]};
+                  }
                   ++c;
                 }
               }
@@ -1338,6 +1378,15 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       }
       if (lane == 0)
         atomicAdd(&g_x1_stamps[grp * (kStampSeg + kStampCnt) + kStampSeg], ecnt[0]);
+      if constexpr (S16) {  // the lanes' event counts, one atomic per wave and bin
+        const int bin = nev < kStampHist ? nev : kStampHist - 1;
+        for (int v = 0; v < kStampHist; ++v) {
+          const unsigned long long m = __ballot(bin == v);
+          if (lane == 0 && m)
+            atomicAdd(&g_x1_stamps[2 * (kStampSeg + kStampCnt) + 2 + (chunk == 1 ? 0 : kStampHist) + v],
+                      (unsigned long long)__popcll(m));
+        }
+      }
     }
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain before the workgroup exits
@@ -1353,7 +1402,9 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   for (int qb = 0; qb < NQB; ++qb) {
     const int64_t g =
         (int64_t)(qt * kT + 64 * wq + (S16 ? 16 * qb + (ln & 15) : 32 * qb + (ln & 31))) * P + pl0;
-    if constexpr (S16) {
+    if constexpr (VS_X1_P(256) && DUMP) {
+      asm volatile("" ::"v"(dc[qb]), "v"(g));  // no stores: the count stays as it was
+    } else if constexpr (S16) {
       // lanes l and l ^ 32 hold the same count of the same list: one writes it
       if (ln < 32) dcount[g] = dc[qb];
     } else if (DUMP || (HYB && t1 > t0)) {

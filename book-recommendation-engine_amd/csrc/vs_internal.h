@@ -174,9 +174,9 @@ constexpr int64_t kI8MaxLd = 131072;
 int x1_list_len(int need);
 // Entries per lane list of the filter pass (8).
 int x1_lane_len();
-// Diagnostic: the per-segment cycle sums of a VS_X1_STAMP build (26 values:
-// [2 groups][9 segments + 3 epilogue counts] + steps per group); zeros in a
-// real build.
+// Diagnostic: the per-segment cycle sums of a VS_X1_STAMP build (58 values:
+// [2 groups][9 segments + 3 epilogue counts] + steps per group + two
+// histograms of dump events per lane and launch); zeros in a real build.
 hipError_t x1_stamps(unsigned long long* out, int reset);
 // Diagnostic: the launch plan of a pass (x1_plan, vs_gemm_x1.hip) in
 // vs_x1_plan's layout (include/vsearch.h); touches no device.  dump32 as in

@@ -369,11 +369,13 @@ int vs_filter_wide_sets(int64_t* entries, int64_t* rescored);
 int vs_filter_dump_stats(int64_t* dumps, int64_t* overflows);
 int vs_timer_reset(void);
 /* Diagnostic only (no reference interface): the filter pass's per-segment
- * cycle sums of a stamp build (VS_X1_STAMP=1; zeros otherwise), 26 values:
+ * cycle sums of a stamp build (VS_X1_STAMP=1; zeros otherwise), 58 values:
  * [waves 0-3 | 4-7][load issue, vmcnt wait, barrier 1, matrix issue,
  * barrier 2, epilogue, epilogue reject, factor loads, keys and inserts;
  * factor-load paths, inserting blocks, inserts]
- * then the steps of each group; reset != 0 clears them. */
+ * then the steps of each group, then the 16x16x64 dump launches' events per
+ * lane and launch as two histograms of 0 .. 15+ (the pass's first dump launch,
+ * the later ones); reset != 0 clears them. */
 int vs_x1_stamps(unsigned long long* out, int reset);
 /* Diagnostic only (no reference interface; touches no device): the launches
  * of one filter pass over ntotal rows in nsplit workgroup splits, as the

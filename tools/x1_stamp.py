@@ -21,7 +21,7 @@ index.add_synthetic(n, seed=1234)
 xq = synthetic_rows(50_000_000, 4096, 1536, 5678)
 index.search(xq, 10)
 lib = _lib.load()
-buf = (ctypes.c_ulonglong * 26)()
+buf = (ctypes.c_ulonglong * 58)()
 lib.vs_x1_stamps(buf, 1)
 for _ in range(3):
     index.search(xq, 10)
@@ -40,3 +40,10 @@ for g, label in enumerate(("waves 0-3", "waves 4-7")):
     tiles = steps / 24.0
     print(f"   per tile ({tiles_note}): factor loads {cnts[0] / tiles:.3f}, "
           f"inserting blocks {cnts[1] / tiles:.3f}, inserts {cnts[2] / tiles:.3f}")
+# 16x16x64 dump launches: events (rows that take a slot) per lane and launch
+for row, label in enumerate(("first dump launch", "later dump launches")):
+    h = [buf[26 + 16 * row + i] for i in range(16)]
+    tot = max(1, sum(h))
+    print(f"events per lane, {label} ({sum(h)} lane-launches, mean "
+          f"{sum(i * v for i, v in enumerate(h)) / tot:.3f}; last bin = 15 or more):")
+    print("   " + " ".join(f"{i}:{100.0 * v / tot:.3f}%" for i, v in enumerate(h)))
