@@ -63,11 +63,9 @@ int run_selected(vs_index* idx, const vs_selector* sel, const SearchArgs& a, boo
   Scratch scr(st);
   Partials part;
   part.KP = KP;
-  const bool gemv_fits =
-      (size_t)kGemvMaxQ * idx->ld * sizeof(float) + 4 * kGemvMaxQ * 64 * 8 <= 64 * 1024;
-  if (streaming && gemv_fits) {
+  if (streaming && gemv_fits(idx->ld)) {
     const int gmode = a.mode == MODE_L2 ? MODE_L2D : MODE_IP;
-    const int nblocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (count + 255) / 256));
+    const int nblocks = stream_blocks(count);
     part.P = nblocks;
     const int nql = a.nq <= 2 ? a.nq : (a.nq <= 4 ? 4 : kGemvMaxQ);
     const size_t n = (size_t)nql * part.P * KP;

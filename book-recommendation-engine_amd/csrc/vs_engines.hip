@@ -9,13 +9,48 @@ using namespace vs::host;
 
 namespace {
 
-// The wide verification of flagged queries (VS_X1_WIDE=0 turns it off, for A/B).
-bool wide_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("VS_X1_WIDE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+// The environment switches of this unit (all for A/B runs and the equality
+// tests; the defaults are the product).  "Read": `process` = once, at the
+// first search of the process, and kept; `search` = at every search, never per
+// launch, so a test may flip it between two searches of one process.
+//
+//  name              values (default)           read     what                            flipped by
+//  VS_ENGINE         fp32|bf16v|i8v (auto)      search   the engine of indexes left on   -
+//                                                        VS_ENGINE_AUTO
+//  VS_X1_WIDE        0|1 (1)                    process  wide verification of flagged    -
+//                                                        queries
+//  VS_X1_DUMP        0|1 (1)                    process  dump launches in the filter     tools/ab_dump.sh
+//                                                        pass (0: list launches only)
+//  VS_X1_DUMP_MFMA   32 (16)                    search   MFMA shape of the int8 IP dump  test_gpu_dump_shape,
+//                                                        launches                        test_x1_plan_host
+//  VS_X1_RECUT       0|1|2 (1)                  search   query cuts after every replay   test_gpu_cut_refresh,
+//                                                        (0 once, 2 separate kernels)    test_gpu_exact_cut
+//  VS_X1_ECUT        0|1 (1)                    search   exact-key cuts of the int8 IP   test_gpu_exact_cut
+//                                                        pass over fp32 rows
+//  VS_X1_WGS         n > 0 (256 / 512)          search   workgroups per filter-pass      -
+//                                                        launch (plan_stage)
+//  VS_X1_SPLIT_MULT  n > 1 (1)                  process  times as many database splits   -
+//  VS_SMALL_BATCH    gemv|skinny (by shape)     process  kernel of small exact batches   -
+//  VS_SMALL_FILTER   0|1 (1)                    search   small batches through the       test_gpu_parity
+//                                                        staged engine
+//  VS_SMALL_L2D      0|1 (1)                    search   ... L2 calls under 20 queries   -
+//                                                        too
+//  VS_SKINNY_DEEP    0|1 (1)                    search   the deep stage's small-count    test_gpu_parity
+//                                                        kernel
+//  VS_TAIL_WAIT      0|1 (1)                    search   read the flagged count, skip    test_gpu_cut_refresh,
+//                                                        empty later stages              test_gpu_exact_cut,
+//                                                                                        test_gpu_streams
+//  VS_EXACT_STREAM   0|1 (1)                    search   exact-key stream behind the     -
+//                                                        last stage's fp32 bound
+// On/off switches parse as env_on: unset or a nonzero number is on
+// (VS_X1_WIDE went by its first character once; no tool or test sets it).
+bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return !e || atoi(e) != 0;
+}
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
 int engine_from_env() {
@@ -26,6 +61,57 @@ int engine_from_env() {
   if (strcmp(e, "i8v") == 0) return VS_ENGINE_I8_VERIFY;
   return VS_ENGINE_AUTO;
 }
+// The wide verification of flagged queries.
+bool wide_enabled() {
+  static const bool on = env_on("VS_X1_WIDE");
+  return on;
+}
+// Dump launches in the filter pass (0: every launch a list launch).
+bool dump_enabled() {
+  static const bool on = env_on("VS_X1_DUMP");
+  return on;
+}
+// The MFMA shape of the int8 inner-product dump launches (vs_gemm_x1.hip,
+// x1_has_s16): 16x16x64 by default, 32 runs them on the 32x32x32 form.  Both
+// forms leave the same lists.
+bool dump_mfma32() { return env_int("VS_X1_DUMP_MFMA", 0) == 32; }
+// Query cuts taken again after every replay of a cutting pass (0 sets them
+// once, after the list launch; 2 refreshes them with the separate replay and
+// cut kernels instead of the fused one).
+int recut_mode() {
+  const int v = env_int("VS_X1_RECUT", 1);
+  return v == 0 ? 0 : v == 2 ? 2 : 1;
+}
+// Exact-key cuts of the int8 inner-product pass over fp32 rows (0 keeps
+// a_M + 2B alone).
+bool ecut_enabled() { return env_on("VS_X1_ECUT"); }
+// The filter pass's workgroup target (plan_stage; 0: its default).
+int x1_wgs_env() { return env_int("VS_X1_WGS", 0); }
+// More (shorter) database splits = more lane lists per query.
+int x1_split_mult() {
+  static const int mult = std::max(env_int("VS_X1_SPLIT_MULT", 1), 1);
+  return mult;
+}
+// The kernel of small exact batches: "gemv" / "skinny" (null: by shape).
+const char* small_batch_pref() {
+  static const char* pref = getenv("VS_SMALL_BATCH");
+  return pref;
+}
+// Small batches through the staged engine's skinny passes (0 keeps the exact
+// streaming kernels), over indexes of at least kSmallFilterMinRows rows.
+constexpr int64_t kSmallFilterMinRows = 1 << 18;
+bool small_filter_on() { return env_on("VS_SMALL_FILTER"); }
+// L2 calls of fewer than 20 queries (faiss's sequential formula: the
+// verification rescored with MODE_L2D) through the planes too (0 keeps them on
+// the exact GEMV).
+bool small_l2d_ok(int mode, const SearchArgs& a) {
+  return !(mode == MODE_L2 && a.l2_direct) || env_on("VS_SMALL_L2D");
+}
+// The deep stage's small-count kernel.
+bool skinny_deep_on() { return env_on("VS_SKINNY_DEEP"); }
+// The exact-key stream behind the last stage's fp32 bound (run_gemm_rescored,
+// run_paged; 0 keeps the fp32 GEMM's candidates / pages).
+bool exact_stream_on() { return env_on("VS_EXACT_STREAM"); }
 
 // The exact engine on fp32 / bf16 rows: the fused MFMA GEMM + merge.  With
 // qlist/qcount, the batch is the gathered queries qlist[0 .. *qcount)
@@ -39,9 +125,7 @@ int run_gemm(vs_index* idx, const SearchArgs& a, int need, hipStream_t st,
   part.KP = KP;
   const int nqt = a.nq_pad / kBQ;
   const int ntiles = (ntotal + kBN - 1) / kBN;
-  // A gathered batch of unknown size spreads each query tile over the chip.
-  const int nsplit = qlist ? (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, 256))
-                           : gemm_nsplit(ntiles, nqt);
+  const int nsplit = qlist ? gathered_nsplit(ntiles) : gemm_nsplit(ntiles, nqt);
   part.P = 2 * nsplit;
   const size_t n = (size_t)a.nq_pad * part.P * KP;
   VS_HIP(scr.alloc((void**)&part.key, n * sizeof(float)), "vs: scratch");
@@ -66,95 +150,9 @@ int run_paged(vs_index* idx, const SearchArgs& a, hipStream_t st, const int* gl 
 int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int plane,
                       hipStream_t st, const int* gl, const int* gc);
 
-// The filter-and-verify engine (vs_gemm_x1.hip), entirely stream-ordered, as a
-// chain of stages over the planes the index holds (int8, then bf16):
-//  1. convert the stage's queries to its plane (int8 codes + scales, or bf16);
-//     the x1 pass keeps 8-entry lane lists per query;
-//  2. merge them to the KF best approximate candidates;
-//  3. verify_rescore: exact keys of the candidates + the bound check (fail[]);
-//  4. the flagged queries are compacted on the device and re-checked by the
-//     wide verification (every lane-list entry below the list floors);
-//  5. the merges emit (D, I) of the stage's queries;
-//  6. the queries still flagged go to the next stage as a gathered batch
-//     (device-side list and count: the int8 plane's wider bound leaves
-//     clustered data to the bf16 plane), and after the last plane to the exact
-//     fp32 engine (a launch whose tiles past the device-side count exit at
-//     once), whose rows overwrite theirs.
-// Counts live in device memory; the host reads one only to skip the later
-// stages when none is left (tail_wait_on).  `gl` / `gc` (stages after the first): the batch is queries gl[0 .. *gc) of `a`.
-// dump launches in the filter pass (default; env VS_X1_DUMP=0 runs every
-// launch as a list launch, for A/B)
-static bool dump_enabled() {
-  static const bool v = [] {
-    const char* e = getenv("VS_X1_DUMP");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-
-// The MFMA shape of the int8 inner-product dump launches (vs_gemm_x1.hip,
-// x1_has_s16): 16x16x64 by default; env VS_X1_DUMP_MFMA=32 runs them on the
-// 32x32x32 form (A/B and the equality tests; read once per search, beside the
-// dump switch — never per launch).  Both forms leave the same lists.
-static bool dump_mfma32() {
-  const char* e = getenv("VS_X1_DUMP_MFMA");
-  return e && atoi(e) == 32;
-}
-
-// Query cuts taken again after every replay of a cutting pass (default; env
-// VS_X1_RECUT=0 sets them once, after the list launch; 2 refreshes them with
-// the separate replay and cut kernels instead of the fused one; A/B, read at
-// every search)
-static int recut_mode() {
-  const char* e = getenv("VS_X1_RECUT");
-  const int v = e ? atoi(e) : 1;
-  return v == 0 ? 0 : v == 2 ? 2 : 1;
-}
-
-// Exact-key cuts of the int8 inner-product pass over fp32 rows (default; env
-// VS_X1_ECUT=0 keeps a_M + 2B alone, for A/B; read once per search, beside the
-// dump switch)
-static bool ecut_enabled() {
-  const char* e = getenv("VS_X1_ECUT");
-  return !e || atoi(e) != 0;
-}
-
-// Small batches through the staged engine's skinny passes (env
-// VS_SMALL_FILTER=0 keeps the exact streaming kernels, for A/B; read at every
-// search), over indexes of at least kSmallFilterMinRows rows.
-constexpr int64_t kSmallFilterMinRows = 1 << 18;
-bool small_filter_on() {
-  const char* e = getenv("VS_SMALL_FILTER");
-  return !e || atoi(e) != 0;
-}
-// L2 calls of fewer than 20 queries (faiss's sequential formula: the
-// verification rescored with MODE_L2D) through the planes too (env
-// VS_SMALL_L2D=0 keeps them on the exact GEMV, for A/B)
-bool small_l2d_ok(int mode, const SearchArgs& a) {
-  if (!(mode == MODE_L2 && a.l2_direct)) return true;
-  const char* e = getenv("VS_SMALL_L2D");
-  return !e || atoi(e) != 0;
-}
-
-// The deep stage's small-count kernel (env VS_SKINNY_DEEP=0 turns it off,
-// for A/B; read at every search).
-bool skinny_deep_on() {
-  const char* e = getenv("VS_SKINNY_DEEP");
-  return !e || atoi(e) != 0;
-}
-
-// Workgroups per filter-pass launch the database splits aim at: one round (256,
-// one per CU) for batches of at most 8 query tiles, whose lane lists stay at
-// 128+ per query (C2, 4 query tiles: 256 lists, 405-407k -> 436-441k
-// queries/s, profiles/r06wgs); two rounds (512) above, where one round would
-// cut the lists to 64 per query and saturate some (the 1.25M-row rank of an
-// 8-GPU C3: 11 queries per search to the deep stage, 441k -> 423k).  Env
-// VS_X1_WGS overrides (A/B; read at every search).
-static int x1_wg_target(int nqt) {
-  const char* e = getenv("VS_X1_WGS");
-  const int v = e ? atoi(e) : 0;
-  return v > 0 ? v : nqt <= 8 ? 256 : 512;
-}
+int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipStream_t st,
+                      int plane, bool last_plane, bool deep = false, const int* gl = nullptr,
+                      const int* gc = nullptr);
 
 // Whether a search reads the count of queries a stage leaves flagged (a 4-byte
 // copy to pinned memory and a wait on the stream) and enqueues the later stages
@@ -162,11 +160,10 @@ static int x1_wg_target(int nqt) {
 // device-output calls wait too: the later stages over an empty count are ~45
 // launches of ~5 us each (0.25 ms of a 2.39-ms C2 search, 0.58 ms of the
 // 1.25M-row rank's 10.5 ms, profiles/r06tl), far more than the wait.  Not on a
-// capturing stream (a graph keeps every launch).  Env VS_TAIL_WAIT=0 keeps
-// every launch (A/B; read at every search).
-static bool tail_wait_on(const SearchArgs& a, hipStream_t st) {
-  const char* e = getenv("VS_TAIL_WAIT");
-  if (e && atoi(e) == 0) return false;
+// capturing stream (a graph keeps every launch).  VS_TAIL_WAIT=0 keeps every
+// launch.
+bool tail_wait_on(const SearchArgs& a, hipStream_t st) {
+  if (!env_on("VS_TAIL_WAIT")) return false;
   if (a.host_wait) return true;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
@@ -178,7 +175,7 @@ static bool tail_wait_on(const SearchArgs& a, hipStream_t st) {
 
 // The device-side count *dcount once the stream has reached this point (one
 // pinned int per host thread).
-static int read_count(const int* dcount, hipStream_t st, int* out) {
+int read_count(const int* dcount, hipStream_t st, int* out) {
   static thread_local int* pin = nullptr;
   if (!pin) VS_HIP(hipHostMalloc((void**)&pin, sizeof(int), hipHostMallocPortable), "vs: count");
   VS_HIP(hipMemcpyAsync(pin, dcount, sizeof(int), hipMemcpyDeviceToHost, st), "vs: count");
@@ -187,105 +184,116 @@ static int read_count(const int* dcount, hipStream_t st, int* out) {
   return VS_OK;
 }
 
-int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipStream_t st,
-                      int plane, bool last_plane, bool deep = false, const int* gl = nullptr,
-                      const int* gc = nullptr) {
-  const int ntotal = (int)idx->ntotal;
-  const int mode = a.mode;
-  const bool gathered = gl != nullptr;
-  Scratch scr(st);
+// One stage of the filter-and-verify engine: what its steps (below, in the
+// order run_filter_verify calls them) share.  Scratch is a bump allocator and
+// everything is stream-ordered, so the steps' order of allocations and
+// launches is part of the result.
+struct Stage {
+  vs_index* idx;
+  const SearchArgs& a;
+  hipStream_t st;
+  const int need, KF, plane;
+  const bool last_plane, deep;
+  const int *gl, *gc;   // stages after the first: the batch is queries gl[0 .. *gc) of `a`
+  const bool gathered;  // gl != nullptr
+  const bool i8;        // plane == FILTER_I8
+  // L2: the pass is the inner product of the augmented rows and queries
+  // (vs_index::aug_m, either plane); its lists are mapped to L2 keys after it
+  const bool aug;
+  const int kmode;  // the pass's own metric
+  // the verification's exact keys: an L2 call of fewer than 20 queries takes
+  // faiss's sequential formula (the rounded exact sum of (x - q)^2), larger
+  // ones its BLAS formula
+  const int vmode;
+  const int ntotal;
+  const int L;  // x1_lane_len()
+  Scratch scr;
+  bool small = false;  // StagePlan::small
+  int nq = 0;          // slots of this stage
+  int qa_rows = 0;     // rows of Q / qaux
   X1Args x;
-  x.nq_pad = (int)round_up(a.nq_pad, kX1Q);
-  const int nq = gathered ? x.nq_pad : a.nq;  // slots of this stage
-  const int nqt = x.nq_pad / kX1Q;
-  const int ntiles = (ntotal + kX1Q - 1) / kX1Q;
-  const int L = x1_lane_len();
-  // enough lists that their 4*nsplit*L entries cover 16*KF candidates (C4's
-  // self-join, KF = 64: 128 lists, which lets the int8 stage settle it: 283k ->
-  // 372k students/s, profiles/r02zc), and the workgroup target (x1_wg_target:
-  // two per CU on 256 CUs at C3, 128 lists per query; one per CU up to 8 query
-  // tiles).  More lists put the wide check's floor T (the best last entry of a
-  // full list) deeper behind the top-M, which the bound needs on clustered data
-  // and on the int8 plane (profiles/r02l_ab_split.txt; one workgroup per CU left
-  // 0.7 % of the C3 queries to the exact engine on int8)
-  // Inner product past k = 32 (M = 2k - 1 of 59 .. 127, KF = 64 / 128) takes
-  // twice as many lists again: at C3 (B = 4096) k = 30 left 13 queries per
-  // search and k = 60 815 to the deep bf16 stage (a 10M-row pass of ~20-30 ms
-  // however few they are); with 8 KF / L lists 0 and 26 (60.5 vs 78.9 and 85.9
-  // vs 94.2 ms per search, profiles/r05q, VS_X1_SPLIT_MULT=2)
-  const int lists_per_cand = mode == MODE_IP && KF >= 64 ? 8 : 4;
-  const int wg_target = x1_wg_target(nqt);
-  x.nsplit = (int)std::max<int64_t>(
-      std::min<int64_t>(ntiles, lists_per_cand * ((KF + L - 1) / L)),
-      std::min<int64_t>(ntiles, (wg_target + nqt - 1) / nqt));
-  // the deep stage (a gathered batch of the few queries an earlier stage could
-  // not settle): as many lists as two workgroups per CU give ONE query tile, so
-  // the floors sit far behind the top (the a_M + 2B threshold keeps the wide
-  // set small)
-  // (lane lists of at most ~1 GB: x.nq_pad slots x 4 nsplit lists x 8 entries x 8 B)
-  if (deep)
-    x.nsplit = (int)std::max<int64_t>(
-        x.nsplit, std::min<int64_t>({ntiles, 512, (1ll << 30) / ((int64_t)x.nq_pad * 4 * 8 * 8)}));
-  // A first pass on the bf16 plane (the adaptive order's choice when int8
-  // hands on too many: embedding-like clustered rows) takes twice the lists:
-  // its checks then settle more queries and fewer go to the deep stage
-  // (clustered C3 37.1k -> 43.0k queries/s; on uniform rows the int8 pass
-  // loses 3 % with them; profiles/r05s)
-  if (!gathered && !deep && plane == FILTER_BF16)
-    x.nsplit = (int)std::min<int64_t>(ntiles, 2 * (int64_t)x.nsplit);
-  // A small batch (at most skinny_plane_max_queries() queries, the first stage
-  // of a search routed here by run_topk) streams its plane once through
-  // skinny_plane_topk instead of an x1 pass over a whole query tile: 2,048
-  // lists of 8 per query, the deep stage's count
-  const bool small = !gathered && !deep && a.nq <= skinny_plane_max_queries() && a.self0 < 0 &&
-                     (mode == MODE_IP || (mode == MODE_L2 && idx->l2aug()));  // the pass's IP
-  if (small) x.nsplit = (int)std::min<int64_t>(512, std::max<int64_t>(1, (ntiles + 3) / 4));
-  x.nsplit = std::max(x.nsplit, 1);
-  {  // A/B: more (shorter) database splits = more lane lists per query
-    static const int mult = [] {
-      const char* e = getenv("VS_X1_SPLIT_MULT");
-      return e && atoi(e) > 1 ? atoi(e) : 1;
-    }();
-    x.nsplit = (int)std::min<int64_t>(ntiles, (int64_t)x.nsplit * mult);
-  }
   Partials part;  // lane lists: L entries each
-  part.KP = L;
-  part.P = 4 * x.nsplit;
-  const size_t np_ = (size_t)x.nq_pad * part.P * part.KP;
-  VS_HIP(scr.alloc((void**)&part.key, np_ * sizeof(float)), "vs: scratch");
-  VS_HIP(scr.alloc((void**)&part.id, np_ * sizeof(int)), "vs: scratch");
   // this stage's fp32 query rows and aux values: the staged batch, the stored
   // rows (self-joins), or a gathered copy of the flagged ones
-  const float* Q = a.self0 >= 0 ? (const float*)idx->row(a.self0) : a.qbuf;
-  const float* qaux = a.qaux;
+  const float* Q = nullptr;
+  const float* qaux = nullptr;
+  const float* qs = nullptr;   // int8: query scales
+  const float* qr2 = nullptr;  // int8: query residual norms (for the bound)
   int* qrow = nullptr;
+  const unsigned* stats = nullptr;  // the index's maxima (kept by add / remove)
+  BoundArgs ba;
+  int* qlist = nullptr;   // merge_and_verify: the queries still flagged, as slots of this stage
+  int* qcount = nullptr;  // [0] after the first check, [1] after the wide one
+
+  Stage(vs_index* idx_, const SearchArgs& a_, int need_, int KF_, hipStream_t st_, int plane_,
+        bool last_plane_, bool deep_, const int* gl_, const int* gc_)
+      : idx(idx_), a(a_), st(st_), need(need_), KF(KF_), plane(plane_), last_plane(last_plane_),
+        deep(deep_), gl(gl_), gc(gc_), gathered(gl_ != nullptr), i8(plane_ == FILTER_I8),
+        aug(a_.mode == MODE_L2 && idx_->l2aug()), kmode(aug ? MODE_IP : a_.mode),
+        vmode(a_.mode == MODE_L2 && a_.l2_direct ? MODE_L2D : a_.mode), ntotal((int)idx_->ntotal),
+        L(x1_lane_len()), scr(st_) {}
+};
+
+// Step 0: the stage's sizes (plan_stage, vs_host.h) and its lane lists.
+int size_lists(Stage& s) {
+  StageShape sh;
+  sh.mode = s.a.mode;
+  sh.plane = s.plane;
+  sh.KF = s.KF;
+  sh.nq = s.a.nq;
+  sh.nq_pad = s.a.nq_pad;
+  sh.ntotal = s.ntotal;
+  sh.gathered = s.gathered;
+  sh.deep = s.deep;
+  sh.self_join = s.a.self0 >= 0;
+  sh.l2aug = s.idx->l2aug();
+  sh.L = s.L;
+  sh.skinny_max_q = skinny_plane_max_queries();
+  sh.wgs_env = x1_wgs_env();
+  sh.split_mult = x1_split_mult();
+  const StagePlan p = plan_stage(sh);
+  s.small = p.small;
+  s.x.nq_pad = p.nq_pad;
+  s.x.nsplit = p.nsplit;
+  s.nq = s.gathered ? p.nq_pad : s.a.nq;
+  s.part.KP = s.L;
+  s.part.P = 4 * p.nsplit;
+  const size_t np_ = (size_t)p.nq_pad * s.part.P * s.part.KP;
+  VS_HIP(s.scr.alloc((void**)&s.part.key, np_ * sizeof(float)), "vs: scratch");
+  VS_HIP(s.scr.alloc((void**)&s.part.id, np_ * sizeof(int)), "vs: scratch");
+  return VS_OK;
+}
+
+// Step 1: the stage's queries — the gathered copy, their plane (a conversion,
+// or the stored rows' own), the int8 factors — and the pass's arguments.
+int stage_queries(Stage& s) {
+  vs_index* idx = s.idx;
+  const SearchArgs& a = s.a;
+  Scratch& scr = s.scr;
+  X1Args& x = s.x;
+  hipStream_t st = s.st;
+  const int mode = a.mode, plane = s.plane;
+  const bool gathered = s.gathered, i8 = s.i8, aug = s.aug;
+  s.Q = a.self0 >= 0 ? (const float*)idx->row(a.self0) : a.qbuf;
+  s.qaux = a.qaux;
   if (gathered) {
     float *qc = nullptr, *ac = nullptr;
     VS_HIP(scr.alloc((void**)&qc, (size_t)x.nq_pad * idx->ld * sizeof(float)), "vs: scratch");
     VS_HIP(scr.alloc((void**)&ac, (size_t)x.nq_pad * sizeof(float)), "vs: scratch");
-    VS_HIP(scr.alloc((void**)&qrow, (size_t)x.nq_pad * sizeof(int)), "vs: scratch");
-    VS_HIP(launch_gather_queries(Q, idx->ld, a.qaux, gl, gc, x.nq_pad, a.self0, qc, ac, qrow, st),
+    VS_HIP(scr.alloc((void**)&s.qrow, (size_t)x.nq_pad * sizeof(int)), "vs: scratch");
+    VS_HIP(launch_gather_queries(s.Q, idx->ld, a.qaux, s.gl, s.gc, x.nq_pad, a.self0, qc, ac,
+                                 s.qrow, st),
            "vs: gathered queries");
-    Q = qc;
-    qaux = ac;
+    s.Q = qc;
+    s.qaux = ac;
   }
+  const float* Q = s.Q;
   const bool self_rows = a.self0 >= 0 && !gathered;  // queries are stored rows in place
-  const int qa_rows = gathered ? x.nq_pad : a.nq_pad;  // rows of Q / qaux
+  const int qa_rows = s.qa_rows = gathered ? x.nq_pad : a.nq_pad;
   // query plane: a conversion of the stage's queries, or the stored rows' plane
-  const bool i8 = plane == FILTER_I8;
-  // L2: the pass is the inner product of the augmented rows and queries
-  // (vs_index::aug_m, either plane); its lists are mapped to L2 keys after it
-  const bool aug = mode == MODE_L2 && idx->l2aug();
   if (aug && (idx->aug_m <= 0 || self_rows)) return fail(VS_E_INVALID, "vs: int8 L2 plane");
-  const int kmode = aug ? MODE_IP : mode;  // the pass's own metric
-  // the verification's exact keys: an L2 call of fewer than 20 queries takes
-  // faiss's sequential formula (the rounded exact sum of (x - q)^2), larger
-  // ones its BLAS formula
-  const int vmode = mode == MODE_L2 && a.l2_direct ? MODE_L2D : mode;
   const int64_t pb = idx->planebytes(plane);
   const char* QH = nullptr;
-  const float* qs = nullptr;    // int8: query scales
-  const float* qr2 = nullptr;   // int8: query residual norms (for the bound)
   // stored rows starting on a tile boundary are read from the index's own
   // (tile-major) plane; any other batch is converted (the same codes)
   const bool plane_rows = self_rows && a.self0 % kX1Q == 0;
@@ -293,8 +301,8 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
   if (plane_rows) {
     QH = idx->fplane[plane];
     if (i8) {
-      qs = idx->fscale + a.self0;
-      qr2 = idx->rn2[FILTER_I8] + a.self0;
+      s.qs = idx->fscale + a.self0;
+      s.qr2 = idx->rn2[FILTER_I8] + a.self0;
     }
   } else {
     char* qh = nullptr;
@@ -310,8 +318,8 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
       else
         VS_HIP(launch_quantize_i8(Q, idx->ld, 0, qa_rows, (int8_t*)qh, sc, r, st),
                "vs: query plane");
-      qs = sc;
-      qr2 = r;
+      s.qs = sc;
+      s.qr2 = r;
     } else if (aug) {
       VS_HIP(launch_bf16_plane_l2aug(Q, idx->ld, 0, qa_rows, idx->aug, nullptr, (uint16_t*)qh,
                                      nullptr, nullptr, st),
@@ -322,7 +330,7 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
     VS_HIP(launch_plane_zero_rows(qh, pb, qa_rows, x.nq_pad - qa_rows, st), "vs: query plane");
     QH = qh;
   }
-  const unsigned* stats = idx->bstats[plane];  // the index's maxima (kept by add / remove)
+  s.stats = idx->bstats[plane];
   x.filter = plane;
   x.XH = idx->fplane[plane];
   x.xs = idx->fscale;
@@ -334,87 +342,102 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
     VS_HIP(launch_mul_arrays(idx->fscale, a.xaux, idx->capacity, cx, st), "vs: cosine factors");
     x.xs = cx;
     if (plane_rows) {
-      qs = cx + a.self0;
+      s.qs = cx + a.self0;
     } else {
       float* cq = nullptr;
       VS_HIP(scr.alloc((void**)&cq, (size_t)qa_rows * sizeof(float)), "vs: scratch");
-      VS_HIP(launch_mul_arrays(qs, qaux, qa_rows, cq, st), "vs: cosine factors");
-      qs = cq;
+      VS_HIP(launch_mul_arrays(s.qs, s.qaux, qa_rows, cq, st), "vs: cosine factors");
+      s.qs = cq;
     }
   }
   if (i8) {  // the per-lane factor bounds of the fast reject (scalar loads in the kernel)
     float* gm = nullptr;
     const size_t ng = (size_t)(idx->capacity / 16);
     VS_HIP(scr.alloc((void**)&gm, 2 * ng * sizeof(float)), "vs: scratch");
-    VS_HIP(launch_group_max(x.xs, idx->capacity, gm, st, ntotal, gm + ng), "vs: factor bounds");
+    VS_HIP(launch_group_max(x.xs, idx->capacity, gm, st, s.ntotal, gm + ng), "vs: factor bounds");
     x.xgmax = gm;
     x.xgmin = gm + ng;
   }
   x.xaux = a.xaux;
   x.QH = QH;
-  x.qs = qs;
-  x.qaux = qaux;
+  x.qs = s.qs;
+  x.qaux = s.qaux;
   x.nqa = qa_rows;
   x.ld = !aug ? idx->ld : i8 ? idx->ld + idx->aug_m : idx->ld + kAugBf16;  // the plane's K
-  x.ntotal = ntotal;
+  x.ntotal = s.ntotal;
   x.self0 = self_rows ? a.self0 : -1;
-  x.qrow = qrow;
-  x.qcount = gc;
-  const BoundArgs ba = aug ? make_bound_args_l2aug(idx->ld, idx->aug, plane)
-                           : make_bound_args(idx->ld, plane);
-  if (!gathered && !small && x1_dump_applies(kmode, plane) && dump_enabled() &&
-      x1_pass_dumps(ntotal, x.nsplit)) {
-    // query cuts + dump launches (vs_gemm_x1.hip header, vs_x1_cuts.hip "Query cuts"): the
-    // cuts are set after the pass's first launch and are the verification's
-    // floor for the rows the dump launches drop.  The dump slots: up to
-    // x1_dump_slots() candidate rows per lane list and segment within ~4 GB;
-    // fewer than 16 (or no memory): every launch is a list launch.
-    const int64_t lists = (int64_t)x.nq_pad * part.P;
-    const int dR = (int)std::min<int64_t>(x1_dump_slots(), (int64_t(4) << 30) / (lists * 8));
-    if (dR >= 16) {
-      int *dc = nullptr, *ds = nullptr;
-      hipError_t e = scr.alloc((void**)&dc, (size_t)lists * sizeof(int));
-      if (e == hipSuccess) e = scr.alloc((void**)&ds, (size_t)lists * dR * 2 * sizeof(int));
-      if (e == hipSuccess) {
-        VS_HIP(scr.alloc((void**)&x.qcut, (size_t)qa_rows * sizeof(float)), "vs: scratch");
-        double* bk = nullptr;
-        VS_HIP(scr.alloc((void**)&bk, (size_t)qa_rows * sizeof(double)), "vs: scratch");
-        VS_HIP(hipMemsetD32Async((hipDeviceptr_t)x.qcut, 0x7f7fffff, (size_t)qa_rows, st),
-               "vs: cuts");
-        VS_HIP(hipMemsetAsync(dc, 0, (size_t)lists * sizeof(int), st), "vs: dumps");
-        VS_HIP(launch_qbound(mode, Q, idx->ld, qaux, plane, stats, qr2, qa_rows, bk, st, &ba),
-               "vs: cuts");
-        x.qbkey = bk;
-        x.qcut_m = need;
-        x.dump = true;
-        x.dump32 = dump_mfma32();
-        x.recut = recut_mode();
-        // exact-key cuts: the int8 inner-product pass of an fp32 index (the
-        // augmented L2 and bf16-plane passes keep a_M + 2B)
-        if (i8 && mode == MODE_IP && idx->esize == 4 && need <= kEcutMaxM && ecut_enabled()) {
-          int* ci = nullptr;
-          VS_HIP(scr.alloc((void**)&x.qam, (size_t)qa_rows * sizeof(float)), "vs: scratch");
-          VS_HIP(scr.alloc((void**)&x.ecut_key, (size_t)qa_rows * kEcutMaxM * sizeof(float)),
-                 "vs: scratch");
-          VS_HIP(scr.alloc((void**)&ci, (size_t)qa_rows * kEcutMaxM * sizeof(int)), "vs: scratch");
-          VS_HIP(hipMemsetD32Async((hipDeviceptr_t)x.qam, 0x7f7fffff, (size_t)qa_rows, st),
-                 "vs: cuts");
-          VS_HIP(hipMemsetAsync(ci, 0xFF, (size_t)qa_rows * kEcutMaxM * sizeof(int), st),
-                 "vs: cuts");
-          x.ecut_id = ci;
-          x.ecut_x = (const float*)idx->codes;
-          x.ecut_q = Q;
-          x.ecut_ld = idx->ld;
-        }
-        x.dcount = dc;
-        x.dslot = ds;
-        x.dR = dR;
-        x.dstats = device_stats(idx->device) ? device_stats(idx->device) + 6 : nullptr;
-      } else {
-        (void)hipGetLastError();  // out of memory for the dumps: list launches
-      }
-    }
+  x.qrow = s.qrow;
+  x.qcount = s.gc;
+  s.ba = aug ? make_bound_args_l2aug(idx->ld, idx->aug, plane) : make_bound_args(idx->ld, plane);
+  return VS_OK;
+}
+
+// Step 1b (a first-stage x1 pass long enough to dump): query cuts + dump
+// launches (vs_gemm_x1.hip header, vs_x1_cuts.hip "Query cuts").  The cuts are
+// set after the pass's first launch and are the verification's floor for the
+// rows the dump launches drop.  The dump slots: up to x1_dump_slots() candidate
+// rows per lane list and segment within ~4 GB; fewer than 16 (or no memory):
+// every launch is a list launch.
+int arm_dumps(Stage& s) {
+  vs_index* idx = s.idx;
+  Scratch& scr = s.scr;
+  X1Args& x = s.x;
+  hipStream_t st = s.st;
+  const int qa_rows = s.qa_rows, need = s.need, mode = s.a.mode;
+  if (s.gathered || s.small || !x1_dump_applies(s.kmode, s.plane) || !dump_enabled() ||
+      !x1_pass_dumps(s.ntotal, x.nsplit))
+    return VS_OK;
+  const int64_t lists = (int64_t)x.nq_pad * s.part.P;
+  const int dR = (int)std::min<int64_t>(x1_dump_slots(), (int64_t(4) << 30) / (lists * 8));
+  if (dR < 16) return VS_OK;
+  int *dc = nullptr, *ds = nullptr;
+  hipError_t e = scr.alloc((void**)&dc, (size_t)lists * sizeof(int));
+  if (e == hipSuccess) e = scr.alloc((void**)&ds, (size_t)lists * dR * 2 * sizeof(int));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // out of memory for the dumps: list launches
+    return VS_OK;
   }
+  VS_HIP(scr.alloc((void**)&x.qcut, (size_t)qa_rows * sizeof(float)), "vs: scratch");
+  double* bk = nullptr;
+  VS_HIP(scr.alloc((void**)&bk, (size_t)qa_rows * sizeof(double)), "vs: scratch");
+  VS_HIP(hipMemsetD32Async((hipDeviceptr_t)x.qcut, 0x7f7fffff, (size_t)qa_rows, st), "vs: cuts");
+  VS_HIP(hipMemsetAsync(dc, 0, (size_t)lists * sizeof(int), st), "vs: dumps");
+  VS_HIP(launch_qbound(mode, s.Q, idx->ld, s.qaux, s.plane, s.stats, s.qr2, qa_rows, bk, st, &s.ba),
+         "vs: cuts");
+  x.qbkey = bk;
+  x.qcut_m = need;
+  x.dump = true;
+  x.dump32 = dump_mfma32();
+  x.recut = recut_mode();
+  // exact-key cuts: the int8 inner-product pass of an fp32 index (the
+  // augmented L2 and bf16-plane passes keep a_M + 2B)
+  if (s.i8 && mode == MODE_IP && idx->esize == 4 && need <= kEcutMaxM && ecut_enabled()) {
+    int* ci = nullptr;
+    VS_HIP(scr.alloc((void**)&x.qam, (size_t)qa_rows * sizeof(float)), "vs: scratch");
+    VS_HIP(scr.alloc((void**)&x.ecut_key, (size_t)qa_rows * kEcutMaxM * sizeof(float)),
+           "vs: scratch");
+    VS_HIP(scr.alloc((void**)&ci, (size_t)qa_rows * kEcutMaxM * sizeof(int)), "vs: scratch");
+    VS_HIP(hipMemsetD32Async((hipDeviceptr_t)x.qam, 0x7f7fffff, (size_t)qa_rows, st), "vs: cuts");
+    VS_HIP(hipMemsetAsync(ci, 0xFF, (size_t)qa_rows * kEcutMaxM * sizeof(int), st), "vs: cuts");
+    x.ecut_id = ci;
+    x.ecut_x = (const float*)idx->codes;
+    x.ecut_q = s.Q;
+    x.ecut_ld = idx->ld;
+  }
+  x.dcount = dc;
+  x.dslot = ds;
+  x.dR = dR;
+  x.dstats = device_stats(idx->device) ? device_stats(idx->device) + 6 : nullptr;
+  return VS_OK;
+}
+
+// Step 1c: the pass — 8-entry lane lists per query from the x1 kernels or a
+// skinny kernel — and, for an augmented pass, its keys mapped to L2.
+int run_pass(Stage& s) {
+  const SearchArgs& a = s.a;
+  X1Args& x = s.x;
+  hipStream_t st = s.st;
+  const bool gathered = s.gathered, i8 = s.i8;
   {
     // the pass as a whole (list + dump launches and the cut / replay kernels
     // between them) under "<name>_pass", beside the per-launch spans
@@ -426,115 +449,176 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
     // the deep bf16 stage of a few queries (inner product / augmented L2, not
     // a self-join): skinny_plane_topk streams the plane once for them and
     // the x1 pass exits, or the reverse, by the device-side count
-    if (gathered && deep && !i8 && kmode == MODE_IP && a.self0 < 0 && skinny_deep_on()) {
-      VS_HIP(launch_skinny_plane(FILTER_BF16, x.XH, x.QH, x.ld, ntotal, gc, nullptr, nullptr, part,
-                                 st),
+    if (gathered && s.deep && !i8 && s.kmode == MODE_IP && a.self0 < 0 && skinny_deep_on()) {
+      VS_HIP(launch_skinny_plane(FILTER_BF16, x.XH, x.QH, x.ld, s.ntotal, s.gc, nullptr, nullptr,
+                                 s.part, st),
              "vs: skinny deep stage");
       x.qskip = skinny_plane_max_queries();
     }
-    if (small) {
+    if (s.small) {
       int* cnt = nullptr;
-      VS_HIP(scr.alloc((void**)&cnt, sizeof(int)), "vs: scratch");
+      VS_HIP(s.scr.alloc((void**)&cnt, sizeof(int)), "vs: scratch");
       VS_HIP(hipMemsetD32Async((hipDeviceptr_t)cnt, a.nq, 1, st), "vs: count");
       KernelTimer ks(st, i8 ? "skinny_plane_topk_i8" : "skinny_plane_topk");
-      VS_HIP(launch_skinny_plane(plane, x.XH, x.QH, x.ld, ntotal, cnt, qs, x.xs, part, st, a.nq),
+      VS_HIP(launch_skinny_plane(s.plane, x.XH, x.QH, x.ld, s.ntotal, cnt, s.qs, x.xs, s.part, st,
+                                 a.nq),
              "vs: skinny first stage");
       ks.stop();
     } else {
       int nd = 0;
-      VS_HIP(launch_gemm_topk_x1(kmode, x, part, st, &nd), "vs: gemm_topk_x1 launch");
+      VS_HIP(launch_gemm_topk_x1(s.kmode, x, s.part, st, &nd), "vs: gemm_topk_x1 launch");
     }
     x.timing = nullptr;
     whole.stop();
   }
-  if (aug)  // augmented inner-product keys A -> L2 keys |q|^2 + 2A (lists and cuts)
-    VS_HIP(launch_l2aug_map(part.key, part.id, (int64_t)part.P * part.KP, qa_rows, qaux,
-                            idx->aug.nref, x.qcut, st),
+  if (s.aug)  // augmented inner-product keys A -> L2 keys |q|^2 + 2A (lists and cuts)
+    VS_HIP(launch_l2aug_map(s.part.key, s.part.id, (int64_t)s.part.P * s.part.KP, s.qa_rows,
+                            s.qaux, s.idx->aug.nref, x.qcut, st),
            "vs: L2 keys");
+  return VS_OK;
+}
 
+// Steps 2-5: the approximate merge, the two verifications with the flagged
+// queries compacted after each, and the merge that emits the stage's (D, I).
+int merge_and_verify(Stage& s) {
+  vs_index* idx = s.idx;
+  const SearchArgs& a = s.a;
+  Scratch& scr = s.scr;
+  hipStream_t st = s.st;
+  const Partials& part = s.part;
+  const int nq = s.nq, KF = s.KF, L = s.L;
   // approximate top-KF per query (plain lexicographic order: the L2 merge)
   float* Dk = nullptr;
   int64_t* Ik = nullptr;
   VS_HIP(scr.alloc((void**)&Dk, (size_t)nq * KF * sizeof(float)), "vs: scratch");
   VS_HIP(scr.alloc((void**)&Ik, (size_t)nq * KF * sizeof(int64_t)), "vs: scratch");
   if (KF > 64) {  // 2k - 1 > 64 (inner product, k > 32): the select kernel
-    VS_HIP(launch_select_lists(part, L, nq, KF, Dk, Ik, st, gc), "vs: merge");
+    VS_HIP(launch_select_lists(part, L, nq, KF, Dk, Ik, st, s.gc), "vs: merge");
   } else if (select_heads_applies(part, L, KF)) {
-    VS_HIP(launch_select_heads(part, nq, KF, Dk, Ik, st, gc), "vs: merge");
+    VS_HIP(launch_select_heads(part, nq, KF, Dk, Ik, st, s.gc), "vs: merge");
   } else {
     Partials mp = part;
     mp.KP = kp_for(KF);
     mp.KL = L;
-    VS_HIP(launch_merge_partials(MODE_L2, mp, nq, KF, 0, 0.0f, Dk, Ik, KF, st, 0, nullptr, gc),
+    VS_HIP(launch_merge_partials(MODE_L2, mp, nq, KF, 0, 0.0f, Dk, Ik, KF, st, 0, nullptr, s.gc),
            "vs: merge");
   }
   Partials vp;
   vp.KP = kp_for(KF);
   vp.P = 1;
   int* flags = nullptr;
-  int* qlist = nullptr;
-  int* qcount = nullptr;
   VS_HIP(scr.alloc((void**)&vp.key, (size_t)nq * vp.KP * sizeof(float)), "vs: scratch");
   VS_HIP(scr.alloc((void**)&vp.id, (size_t)nq * vp.KP * sizeof(int)), "vs: scratch");
   VS_HIP(scr.alloc((void**)&flags, (size_t)nq * sizeof(int)), "vs: scratch");
-  VS_HIP(scr.alloc((void**)&qlist, (size_t)x.nq_pad * sizeof(int)), "vs: scratch");
-  VS_HIP(scr.alloc((void**)&qcount, 2 * sizeof(int)), "vs: scratch");
-  const float* qinv = mode == MODE_COS ? qaux : nullptr;
-  const float* xinv = mode == MODE_COS ? a.xaux : nullptr;
-  VS_HIP(launch_verify_rescore(vmode, nq, KF, need, Dk, Ik, idx->codes, idx->norms, Q, qaux,
-                               idx->ld, ba, stats, part, L, vp.key, vp.id, vp.KP, flags, st, qinv,
-                               xinv, qr2, gc, x.qcut, idx->esize),
-         "vs: verify");
+  VS_HIP(scr.alloc((void**)&s.qlist, (size_t)s.x.nq_pad * sizeof(int)), "vs: scratch");
+  VS_HIP(scr.alloc((void**)&s.qcount, 2 * sizeof(int)), "vs: scratch");
+  VerifyArgs v;  // one fill for both verifications
+  v.mode = s.vmode;
+  v.KF = KF;
+  v.M = s.need;
+  v.X = idx->codes;
+  v.xesize = idx->esize;
+  v.xn = idx->norms;
+  v.Q = s.Q;
+  v.qn = s.qaux;
+  v.ld = idx->ld;
+  v.ba = s.ba;
+  v.stats = s.stats;
+  v.lists = part;
+  v.L = L;
+  v.okey = vp.key;
+  v.oid = vp.id;
+  v.KP = vp.KP;
+  v.fail = flags;
+  v.qinv = a.mode == MODE_COS ? s.qaux : nullptr;
+  v.xinv = a.mode == MODE_COS ? a.xaux : nullptr;
+  v.qr2i8 = s.qr2;
+  v.qcut = s.x.qcut;
+  VS_HIP(launch_verify_rescore(v, nq, Dk, Ik, s.gc, st), "vs: verify");
   unsigned long long* dst = device_stats(idx->device);
   if (!dst) return fail(VS_E_HIP, "vs: statistics buffer");
   // statistics: [0] queries (first stage), [1] flagged by a first check, [2]
   // redone by the exact engine, [3] handed to a second filter stage
-  VS_HIP(launch_compact_flags(flags, nq, qlist, qcount, dst + 1, gathered ? nullptr : dst + 0, st),
+  VS_HIP(launch_compact_flags(flags, nq, s.qlist, s.qcount, dst + 1,
+                              s.gathered ? nullptr : dst + 0, st),
          "vs: flags");
   if (wide_enabled())
-    VS_HIP(launch_verify_wide(vmode, nq, qlist, qcount, KF, need, idx->codes, idx->norms, Q, qaux,
-                              idx->ld, ba, stats, part, L, vp.key, vp.id, vp.KP, flags, st, qinv,
-                              xinv, qr2, Dk, Ik, dst + 4, x.qcut, idx->esize),
-           "vs: verify wide");
-  VS_HIP(launch_compact_flags(flags, nq, qlist, qcount + 1, last_plane ? dst + 2 : dst + 3,
-                              nullptr, st),
+    VS_HIP(launch_verify_wide(v, nq, s.qlist, s.qcount, Dk, Ik, dst + 4, st), "vs: verify wide");
+  VS_HIP(launch_compact_flags(flags, nq, s.qlist, s.qcount + 1,
+                              s.last_plane ? dst + 2 : dst + 3, nullptr, st),
          "vs: flags");
-  VS_HIP(launch_merge_partials(vmode, vp, nq, a.k, idx->id_base, a.min_score, a.D, a.I, a.k, st,
-                               a.raw, gl, gc),
+  VS_HIP(launch_merge_partials(s.vmode, vp, nq, a.k, idx->id_base, a.min_score, a.D, a.I, a.k, st,
+                               a.raw, s.gl, s.gc),
          "vs: merge");
+  return VS_OK;
+}
+
+// Step 6: the queries still flagged go to the next stage — the deep bf16
+// stage, or after the last plane the exact redo — as query ids of `a`.
+int hand_off(Stage& s) {
+  vs_index* idx = s.idx;
+  const SearchArgs& a = s.a;
+  hipStream_t st = s.st;
+  const int* left_count = s.qcount + 1;
   // The first stage's and the deep stage's leftovers, read when the call may
   // wait (tail_wait_on): nothing left, no later stage is enqueued (the live
   // search_catalog path, mcp_book_server.py:142, at batch 1: ~30 launches,
   // 0.13 ms of a 2.6-ms search; C2 ~45, 0.25 ms)
-  if ((!gathered || deep) && tail_wait_on(a, st)) {
-    int left = -1;
-    int rc = read_count(qcount + 1, st, &left);
+  int left = -1;
+  if ((!s.gathered || s.deep) && tail_wait_on(a, st)) {
+    int rc = read_count(left_count, st, &left);
     if (rc) return rc;
-    if (left == 0) {
-      if (!last_plane && !gathered && plane == FILTER_I8) {
-        rc = adaptive_record(idx, qcount + 1, nq, st);
-        if (rc) return rc;
-      }
-      return VS_OK;
-    }
   }
+  // the adaptive order's counters of an int8-first search, whether or not
+  // anything is left (a first stage composes no list, so nothing is enqueued
+  // between the count's read and this)
+  if (!s.last_plane && !s.gathered && s.plane == FILTER_I8) {
+    int rc = adaptive_record(idx, left_count, s.nq, st);
+    if (rc) return rc;
+  }
+  if (left == 0) return VS_OK;
   // what is still flagged (usually nothing: every tile exits), as query ids of `a`
-  const int* next = qlist;
-  if (gathered) {
+  const int* next = s.qlist;
+  if (s.gathered) {
     int* composed = nullptr;
-    VS_HIP(scr.alloc((void**)&composed, (size_t)x.nq_pad * sizeof(int)), "vs: scratch");
-    VS_HIP(launch_compose_list(gl, qlist, qcount + 1, x.nq_pad, composed, st), "vs: flags");
+    VS_HIP(s.scr.alloc((void**)&composed, (size_t)s.x.nq_pad * sizeof(int)), "vs: scratch");
+    VS_HIP(launch_compose_list(s.gl, s.qlist, left_count, s.x.nq_pad, composed, st), "vs: flags");
     next = composed;
   }
-  if (!last_plane) {
-    if (!gathered && plane == FILTER_I8) {
-      int rc = adaptive_record(idx, qcount + 1, nq, st);
-      if (rc) return rc;
-    }
-    return run_filter_verify(idx, a, need, KF, st, FILTER_BF16, true, true, next, qcount + 1);
-  }
+  if (!s.last_plane)
+    return run_filter_verify(idx, a, s.need, s.KF, st, FILTER_BF16, true, true, next, left_count);
   // the exact redo (untimed: the kernel timer holds the first filter pass)
-  return run_gemm_rescored(idx, a, need, KF, plane, st, next, qcount + 1);
+  return run_gemm_rescored(idx, a, s.need, s.KF, s.plane, st, next, left_count);
+}
+
+// The filter-and-verify engine (vs_gemm_x1.hip), entirely stream-ordered, as a
+// chain of stages over the planes the index holds (int8, then bf16):
+//  0. size the stage's lane lists (plan_stage);
+//  1. convert the stage's queries to its plane (int8 codes + scales, or bf16);
+//     the x1 pass keeps 8-entry lane lists per query;
+//  2. merge them to the KF best approximate candidates;
+//  3. verify_rescore: exact keys of the candidates + the bound check (fail[]);
+//  4. the flagged queries are compacted on the device and re-checked by the
+//     wide verification (every lane-list entry below the list floors);
+//  5. the merges emit (D, I) of the stage's queries;
+//  6. the queries still flagged go to the next stage as a gathered batch
+//     (device-side list and count: the int8 plane's wider bound leaves
+//     clustered data to the bf16 plane), and after the last plane to the exact
+//     fp32 engine (a launch whose tiles past the device-side count exit at
+//     once), whose rows overwrite theirs.
+// Counts live in device memory; the host reads one only to skip the later
+// stages when none is left (tail_wait_on).  `gl` / `gc` (stages after the
+// first): the batch is queries gl[0 .. *gc) of `a`.
+int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipStream_t st,
+                      int plane, bool last_plane, bool deep, const int* gl, const int* gc) {
+  Stage s(idx, a, need, KF, st, plane, last_plane, deep, gl, gc);
+  int rc = size_lists(s);                // 0
+  if (!rc) rc = stage_queries(s);        // 1: the queries' plane
+  if (!rc) rc = arm_dumps(s);            //    the cuts and dump slots
+  if (!rc) rc = run_pass(s);             //    the pass
+  if (!rc) rc = merge_and_verify(s);     // 2-5
+  if (!rc) rc = hand_off(s);             // 6
+  return rc;
 }
 
 // The staged engine's last stage: the exact fp32 MFMA GEMM (bf16 rows: the
@@ -548,10 +632,6 @@ int run_filter_verify(vs_index* idx, const SearchArgs& a, int need, int KF, hipS
 // 256 row blocks x KP entries); launches past the device-side count exit.
 constexpr int kExactSlots = 256;
 constexpr int kXPageSlots = 1024;  // run_paged's exact-key pages
-bool exact_stream_on() {
-  const char* e = getenv("VS_EXACT_STREAM");
-  return !e || atoi(e) != 0;
-}
 
 int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int plane,
                       hipStream_t st, const int* gl, const int* gc) {
@@ -565,14 +645,9 @@ int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int 
   Partials part;
   part.KP = KP;
   const int ntiles = (ntotal + kBN - 1) / kBN;
-  const int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, 256));
+  const int nsplit = gathered_nsplit(ntiles);
   part.P = 2 * nsplit;
-  // The gathered queries run in slot windows of at most `cap` slots, so the
-  // lists stay within ~1 GB whatever the batch (a 65,536-student self-join
-  // chunk at KP = 64 would need 16 GB for every slot at once); windows past
-  // the device-side count exit at once (usually all but the first).
-  const int cap = (int)std::min<int64_t>(
-      nslot, std::max<int64_t>(kBQ, ((int64_t)1 << 30) / ((int64_t)part.P * KP * 8) / kBQ * kBQ));
+  const int cap = slot_window_cap(nslot, part.P, KP);  // slots per window
   Scratch scr(st);
   const size_t n = (size_t)cap * part.P * KP;
   VS_HIP(scr.alloc((void**)&part.key, n * sizeof(float)), "vs: scratch");
@@ -601,8 +676,6 @@ int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int 
     if (a.self0 >= 0 || !a.qb16) return fail(VS_E_INVALID, "vs: bf16 last stage");
     VS_HIP(scr.alloc((void**)&qc16, (size_t)cap * idx->ld * sizeof(uint16_t)), "vs: scratch");
   }
-  const float* qinv = a.mode == MODE_COS ? ac : nullptr;
-  const float* xinv = a.mode == MODE_COS ? a.xaux : nullptr;
   const int emode = a.mode == MODE_L2 && a.l2_direct ? MODE_L2D : a.mode;
   // The candidates are proven with the fp32 GEMM's own error bound (no plane
   // residuals: BoundArgs::rows_exact); a query it cannot settle (more than
@@ -624,7 +697,7 @@ int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int 
     VS_HIP(scr.alloc((void**)&ol, (size_t)cap * sizeof(int)), "vs: scratch");
     VS_HIP(scr.alloc((void**)&ewc, sizeof(int)), "vs: scratch");
     ep.KP = kp_for(need);
-    ep.P = (int)std::min<int64_t>(256, std::max<int64_t>(1, ((int64_t)ntotal + 1023) / 1024));
+    ep.P = exact_stream_lists(ntotal);
     // slots per launch: the whole window when its lists fit in ~256 MB (C3:
     // one launch triple over an empty count instead of 16), else kExactSlots
     xslots = (int)std::min<int64_t>(
@@ -643,10 +716,30 @@ int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int 
   Partials sp;
   if (skinny) {
     sp.KP = KP;
-    sp.P = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (ntotal + 255) / 256));
+    sp.P = stream_blocks(ntotal);
     VS_HIP(scr.alloc((void**)&sp.key, (size_t)kSkinnyMaxQ * sp.P * KP * sizeof(float)), "vs: scratch");
     VS_HIP(scr.alloc((void**)&sp.id, (size_t)kSkinnyMaxQ * sp.P * KP * sizeof(int)), "vs: scratch");
   }
+  VerifyArgs v;  // every window's rescoring: no plane residuals, no cuts
+  v.mode = emode;
+  v.KF = KF;
+  v.M = need;
+  v.X = idx->codes;
+  v.xesize = idx->esize;
+  v.xn = idx->norms;
+  v.Q = qc;
+  v.qn = ac;
+  v.ld = idx->ld;
+  v.ba = ba;
+  v.stats = idx->bstats[plane];
+  v.lists = skinny ? sp : part;
+  v.L = KP;
+  v.okey = vp.key;
+  v.oid = vp.id;
+  v.KP = vp.KP;
+  v.fail = flags;
+  v.qinv = a.mode == MODE_COS ? ac : nullptr;
+  v.xinv = a.mode == MODE_COS ? a.xaux : nullptr;
   for (int w0 = 0; w0 < nslot; w0 += cap) {
     const int* wl = gl + w0;  // this window's query ids, wc[0] of them
     VS_HIP(launch_window_count(gc, w0, cap, wc, st), "vs: window");
@@ -670,11 +763,7 @@ int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int 
     VS_HIP(launch_merge_partials(MODE_L2, skinny ? sp : part, skinny ? a.nq : cap, KF, 0, 0.0f, Dk,
                                  Ik, KF, st, 0, nullptr, wc),
            "vs: merge");
-    VS_HIP(launch_verify_rescore(emode, cap, KF, need, Dk, Ik, idx->codes, idx->norms, qc, ac,
-                                 idx->ld, ba, idx->bstats[plane], skinny ? sp : part, KP, vp.key,
-                                 vp.id, vp.KP, flags, st, qinv, xinv, nullptr, wc, nullptr,
-                                 idx->esize),
-           "vs: rescore");
+    VS_HIP(launch_verify_rescore(v, cap, Dk, Ik, wc, st), "vs: rescore");
     VS_HIP(launch_merge_partials(emode, vp, cap, a.k, idx->id_base, a.min_score, a.D, a.I, a.k,
                                  st, a.raw, wl, wc),
            "vs: merge");
@@ -683,18 +772,8 @@ int run_gemm_rescored(vs_index* idx, const SearchArgs& a, int need, int KF, int 
     VS_HIP(launch_compact_flags(flags, cap, fl, fc, dstats ? dstats + 8 : nullptr, nullptr, st),
            "vs: exact stream");
     VS_HIP(launch_compose_list(wl, fl, fc, cap, ol, st), "vs: exact stream");
-    ExactStreamArgs ea;
-    ea.X = (const float*)idx->codes;
-    ea.xn = idx->norms;
-    ea.xinv = xinv;
-    ea.ld = idx->ld;
-    ea.ntotal = ntotal;
-    ea.Q = qc;
-    ea.qaux = ac;
+    ExactStreamArgs ea = make_exact_stream_args(idx, a, qc, ac, fl, fc, xslots);
     ea.qrow = a.self0 >= 0 ? qrow : nullptr;
-    ea.slots = fl;
-    ea.count = fc;
-    ea.nslot = xslots;
     for (int s0 = 0; s0 < cap; s0 += xslots) {
       ea.s0 = s0;
       VS_HIP(launch_window_count(fc, s0, xslots, ewc, st), "vs: exact stream");
@@ -804,10 +883,9 @@ int run_paged(vs_index* idx, const SearchArgs& a, hipStream_t st, const int* gl,
   // entries past the rows in place never exist: the last page is never needed
   const int64_t npages = std::max<int64_t>(1, (std::min<int64_t>(need, ntotal) + 63) / 64);
   const int64_t KA = npages * 64;
-  const bool gemv_fits =
-      (size_t)kGemvMaxQ * idx->ld * sizeof(float) + 4 * kGemvMaxQ * 64 * 8 <= 64 * 1024;
-  const bool l2d = a.mode == MODE_L2 && a.l2_direct && idx->esize == 4 && gemv_fits && a.self0 < 0;
-  const bool gemv = !gathered && a.self0 < 0 && idx->esize == 4 && gemv_fits &&
+  const bool fits = gemv_fits(idx->ld);
+  const bool l2d = a.mode == MODE_L2 && a.l2_direct && idx->esize == 4 && fits && a.self0 < 0;
+  const bool gemv = !gathered && a.self0 < 0 && idx->esize == 4 && fits &&
                     (l2d || (a.mode == MODE_IP && a.nq <= 2));
   // The staged engine's last stage (gathered, fp32 rows): the pages are the
   // exact-key stream's (vs_exact.hip, floored), every key the rescoring's own
@@ -846,7 +924,7 @@ int run_paged(vs_index* idx, const SearchArgs& a, hipStream_t st, const int* gl,
   int nsplit = 1, cap = 0, xslots = 0;
   int* wc = nullptr;
   if (gemv) {
-    part.P = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (ntotal + 255) / 256));
+    part.P = stream_blocks(ntotal);
     VS_HIP(scr.alloc((void**)&part.key, (size_t)kGemvMaxQ * part.P * 64 * sizeof(float)),
            "vs: scratch");
     VS_HIP(scr.alloc((void**)&part.id, (size_t)kGemvMaxQ * part.P * 64 * sizeof(int)),
@@ -857,7 +935,7 @@ int run_paged(vs_index* idx, const SearchArgs& a, hipStream_t st, const int* gl,
     // lists: 1,024 x 256 row blocks x 64 entries = 134 MB), so a page of a
     // 4,096-query search is 4 launch triples, not 16 (they run every search,
     // usually over an empty count)
-    part.P = (int)std::min<int64_t>(256, std::max<int64_t>(1, ((int64_t)ntotal + 1023) / 1024));
+    part.P = exact_stream_lists(ntotal);
     xslots = (int)std::min<int64_t>(kXPageSlots, round_up(std::max(a.nq, 1), kBQ));
     VS_HIP(scr.alloc((void**)&part.key, (size_t)xslots * part.P * 64 * sizeof(float)),
            "vs: scratch");
@@ -866,11 +944,9 @@ int run_paged(vs_index* idx, const SearchArgs& a, hipStream_t st, const int* gl,
     VS_HIP(scr.alloc((void**)&wc, sizeof(int)), "vs: scratch");
   } else {
     const int ntiles = (ntotal + kBN - 1) / kBN;
-    nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, 256));
+    nsplit = gathered_nsplit(ntiles);
     part.P = 2 * nsplit;
-    // gathered slots run in windows whose lists stay within ~1 GB
-    cap = (int)std::min<int64_t>(
-        nrow, std::max<int64_t>(kBQ, ((int64_t)1 << 30) / ((int64_t)part.P * 64 * 8) / kBQ * kBQ));
+    cap = slot_window_cap(nrow, part.P, 64);  // slots per window
     VS_HIP(scr.alloc((void**)&part.key, (size_t)cap * part.P * 64 * sizeof(float)), "vs: scratch");
     VS_HIP(scr.alloc((void**)&part.id, (size_t)cap * part.P * 64 * sizeof(int)), "vs: scratch");
     VS_HIP(scr.alloc((void**)&wc, sizeof(int)), "vs: scratch");
@@ -915,17 +991,7 @@ int run_paged(vs_index* idx, const SearchArgs& a, hipStream_t st, const int* gl,
         continue;
       }
       if (xpages) {  // the active queries in launches of xslots (past the count: exit)
-        ExactStreamArgs ea;
-        ea.X = (const float*)idx->codes;
-        ea.xn = idx->norms;
-        ea.xinv = a.mode == MODE_COS ? a.xaux : nullptr;
-        ea.ld = idx->ld;
-        ea.ntotal = ntotal;
-        ea.Q = qf;
-        ea.qaux = qaux;
-        ea.slots = qlist;
-        ea.count = qcount;
-        ea.nslot = xslots;
+        ExactStreamArgs ea = make_exact_stream_args(idx, a, qf, qaux, qlist, qcount, xslots);
         ea.fkey = fkey;
         ea.fid = fid;
         for (int s0 = 0; s0 < nslot; s0 += xslots) {
@@ -993,8 +1059,11 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
                engine != VS_ENGINE_BF16_VERIFY;
   const bool b16_ok = idx->plane_on[FILTER_BF16] && engine != VS_ENGINE_I8_VERIFY &&
                       (idx->l2aug() ? mode == MODE_L2 && idx->aug_m > 0 : true);
-  const bool staged = idx->esize == 4 && engine != VS_ENGINE_FP32_MFMA && KF > 0 && ntotal > 0 &&
-                      nq > kSkinnyMaxQ && (i8_ok || b16_ok);
+  // what every route through the staged engine needs: fp32 rows, a candidate
+  // count for `need`, and no forced fp32 engine
+  const bool staged_ok =
+      idx->esize == 4 && engine != VS_ENGINE_FP32_MFMA && KF > 0 && ntotal > 0;
+  const bool staged = staged_ok && nq > kSkinnyMaxQ && (i8_ok || b16_ok);
   // Small batches over a large index with a filter plane for the metric (inner
   // product; L2 when faiss would take its BLAS branch): the staged engine with
   // skinny passes (below)
@@ -1014,16 +1083,15 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
   // pass.  Otherwise the skinny MFMA kernel (any metric / dtype, L2 by the norm
   // expansion like faiss's BLAS branch), or the GEMV for one or two inner-product
   // queries on fp32 rows (measured faster there, profiles/r01_small_batch_ab.txt).
-  static const char* pref = getenv("VS_SMALL_BATCH");
+  const char* pref = small_batch_pref();
   const bool small_ok = (mode == MODE_IP || mode == MODE_L2) && a.self0 < 0;
-  const bool gemv_fits =
-      (size_t)kGemvMaxQ * idx->ld * sizeof(float) + 4 * kGemvMaxQ * 64 * 8 <= 64 * 1024;
-  const bool direct = small_ok && mode == MODE_L2 && a.l2_direct && idx->esize == 4 && gemv_fits;
+  const bool fits = gemv_fits(idx->ld);
+  const bool direct = small_ok && mode == MODE_L2 && a.l2_direct && idx->esize == 4 && fits;
   const bool skinny_ok = small_ok && !direct && nq <= kSkinnyMaxQ && KP <= 32 &&
                          (nq <= 16 || KP <= 16) && (idx->ld * idx->esize) % 64 == 0;
-  bool gemv = small_ok && gemv_fits && idx->esize == 4 &&
+  bool gemv = small_ok && fits && idx->esize == 4 &&
               (direct || (mode == MODE_IP && nq <= 2 && !(pref && strcmp(pref, "skinny") == 0)));
-  if (pref && strcmp(pref, "gemv") == 0 && small_ok && gemv_fits && nq <= kGemvMaxQ &&
+  if (pref && strcmp(pref, "gemv") == 0 && small_ok && fits && nq <= kGemvMaxQ &&
       (mode == MODE_IP || direct))
     gemv = true;
   // Small batches over a large fp32 index with a filter plane for the metric
@@ -1042,7 +1110,7 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
   part.KP = KP;
   if (gemv) {
     const int gmode = direct ? MODE_L2D : MODE_IP;
-    const int nblocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (idx->ntotal + 255) / 256));
+    const int nblocks = stream_blocks(idx->ntotal);
     part.P = nblocks;
     const int step = kGemvMaxQ;  // queries per corpus pass
     // the kernel writes lists for its padded query count (1, 2, 4 or 8)
@@ -1065,8 +1133,7 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
     return VS_OK;
   }
   if (skinny_ok) {
-    const int nblocks =
-        (int)std::min<int64_t>(2048, std::max<int64_t>(1, (idx->ntotal + 255) / 256));
+    const int nblocks = stream_blocks(idx->ntotal);
     part.P = nblocks;
     const size_t n = (size_t)nq * part.P * KP;
     VS_HIP(scr.alloc((void**)&part.key, n * sizeof(float)), "vs: scratch");
@@ -1082,7 +1149,7 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
            "vs: merge launch");
     return VS_OK;
   }
-  if (idx->esize == 4 && engine != VS_ENGINE_FP32_MFMA && KF > 0 && ntotal > 0) {
+  if (staged_ok) {
     // the automatic order adapts to how much the int8 stage settles
     if (i8_ok && b16_ok && engine == VS_ENGINE_AUTO) i8_ok = adaptive_use_i8(idx);
     // stages: [int8] -> bf16 with deep lists over what is left -> exact fp32
@@ -1095,8 +1162,7 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
   // every query — the exact fp32 GEMM, its candidates rescored in fp64 — so the
   // keys are the same exact roundings the planes' searches return.
   const int bp = idx->bstats[FILTER_BF16] ? FILTER_BF16 : idx->bstats[FILTER_I8] ? FILTER_I8 : -1;
-  if (idx->esize == 4 && engine != VS_ENGINE_FP32_MFMA && KF > 0 && ntotal > 0 &&
-      nq > kSkinnyMaxQ && bp >= 0) {
+  if (staged_ok && nq > kSkinnyMaxQ && bp >= 0) {
     int* gl = nullptr;
     int* gc = nullptr;
     VS_HIP(scr.alloc((void**)&gl, (size_t)a.nq_pad * sizeof(int)), "vs: scratch");

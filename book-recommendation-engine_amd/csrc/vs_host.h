@@ -321,6 +321,129 @@ int run_topk(vs_index* idx, const SearchArgs& a, hipStream_t st, int force_engin
 inline int gemm_nsplit(int ntiles, int nqt) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (512 + nqt - 1) / nqt));
 }
+// Database splits of an exact GEMM launch over a gathered batch of unknown
+// size: each query tile spread over the chip.
+inline int gathered_nsplit(int ntiles) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, 256));
+}
+// Row blocks (lists per query) of the streaming kernels (GEMV, skinny): 256
+// rows each, at most 2,048.
+inline int stream_blocks(int64_t ntotal) {
+  return (int)std::min<int64_t>(2048, std::max<int64_t>(1, (ntotal + 255) / 256));
+}
+// Row blocks (lists per slot) of the exact-key stream: 1,024 rows each, at
+// most 256.
+inline int exact_stream_lists(int64_t ntotal) {
+  return (int)std::min<int64_t>(256, std::max<int64_t>(1, (ntotal + 1023) / 1024));
+}
+// The gathered queries run in slot windows of at most this many slots (whole
+// query tiles, at least one), so their `lists` lists of KP entries stay within
+// ~1 GB whatever the batch (a 65,536-student self-join chunk at KP = 64 would
+// need 16 GB for every slot at once); windows past the device-side count exit
+// at once (usually all but the first).
+inline int slot_window_cap(int64_t nslot, int lists, int KP) {
+  return (int)std::min<int64_t>(
+      nslot, std::max<int64_t>(kBQ, ((int64_t)1 << 30) / ((int64_t)lists * KP * 8) / kBQ * kBQ));
+}
+// The GEMV kernel stages kGemvMaxQ query rows and its lists in 64 KB of LDS.
+inline bool gemv_fits(int64_t ld) {
+  return (size_t)kGemvMaxQ * ld * sizeof(float) + 4 * kGemvMaxQ * 64 * 8 <= 64 * 1024;
+}
+// The exact-key stream's arguments over the fp32 rows of `idx` for the queries
+// at Q / qaux of a search `a`: slots[0 .. *count) in launches of nslot (the
+// caller sets s0 per launch, and qrow / the floors where it has them).
+inline ExactStreamArgs make_exact_stream_args(const vs_index* idx, const SearchArgs& a,
+                                              const float* Q, const float* qaux, const int* slots,
+                                              const int* count, int nslot) {
+  ExactStreamArgs ea;
+  ea.X = (const float*)idx->codes;
+  ea.xn = idx->norms;
+  ea.xinv = a.mode == MODE_COS ? a.xaux : nullptr;
+  ea.ld = idx->ld;
+  ea.ntotal = (int)idx->ntotal;
+  ea.Q = Q;
+  ea.qaux = qaux;
+  ea.slots = slots;
+  ea.count = count;
+  ea.nslot = nslot;
+  return ea;
+}
+
+// The sizes of one filter-and-verify stage (vs_engines.hip, run_filter_verify):
+// a pure function of the stage's shape, checked without a GPU
+// (tools/host_checks.hip).
+struct StageShape {
+  int mode = MODE_IP, plane = FILTER_I8, KF = 0;
+  int nq = 0, nq_pad = 0;  // the search's queries (SearchArgs)
+  int64_t ntotal = 0;
+  bool gathered = false, deep = false;
+  bool self_join = false;  // SearchArgs::self0 >= 0
+  bool l2aug = false;      // vs_index::l2aug()
+  int L = 8;               // x1_lane_len()
+  int skinny_max_q = 0;    // skinny_plane_max_queries()
+  int wgs_env = 0;         // VS_X1_WGS (0 = default)
+  int split_mult = 1;      // VS_X1_SPLIT_MULT (>= 1)
+};
+struct StagePlan {
+  int nq_pad = 0;  // the stage's query slots, a multiple of kX1Q
+  int nsplit = 0;  // database splits: 4 * nsplit lane lists of L per query
+  bool small = false;  // the pass is skinny_plane_topk, not an x1 pass
+};
+inline StagePlan plan_stage(const StageShape& s) {
+  StagePlan p;
+  p.nq_pad = (int)round_up(s.nq_pad, kX1Q);
+  const int nqt = p.nq_pad / kX1Q;
+  const int64_t ntiles = (s.ntotal + kX1Q - 1) / kX1Q;
+  // enough lists that their 4*nsplit*L entries cover 16*KF candidates (C4's
+  // self-join, KF = 64: 128 lists, which lets the int8 stage settle it: 283k ->
+  // 372k students/s, profiles/r02zc), and the workgroup target (below: two per
+  // CU on 256 CUs at C3, 128 lists per query; one per CU up to 8 query tiles).
+  // More lists put the wide check's floor T (the best last entry of a full
+  // list) deeper behind the top-M, which the bound needs on clustered data and
+  // on the int8 plane (profiles/r02l_ab_split.txt; one workgroup per CU left
+  // 0.7 % of the C3 queries to the exact engine on int8)
+  // Inner product past k = 32 (M = 2k - 1 of 59 .. 127, KF = 64 / 128) takes
+  // twice as many lists again: at C3 (B = 4096) k = 30 left 13 queries per
+  // search and k = 60 815 to the deep bf16 stage (a 10M-row pass of ~20-30 ms
+  // however few they are); with 8 KF / L lists 0 and 26 (60.5 vs 78.9 and 85.9
+  // vs 94.2 ms per search, profiles/r05q, VS_X1_SPLIT_MULT=2)
+  const int lists_per_cand = s.mode == MODE_IP && s.KF >= 64 ? 8 : 4;
+  // Workgroups per filter-pass launch the database splits aim at: one round
+  // (256, one per CU) for batches of at most 8 query tiles, whose lane lists
+  // stay at 128+ per query (C2, 4 query tiles: 256 lists, 405-407k -> 436-441k
+  // queries/s, profiles/r06wgs); two rounds (512) above, where one round would
+  // cut the lists to 64 per query and saturate some (the 1.25M-row rank of an
+  // 8-GPU C3: 11 queries per search to the deep stage, 441k -> 423k).
+  const int wg_target = s.wgs_env > 0 ? s.wgs_env : nqt <= 8 ? 256 : 512;
+  int64_t n = std::max<int64_t>(
+      std::min<int64_t>(ntiles, lists_per_cand * ((s.KF + s.L - 1) / s.L)),
+      std::min<int64_t>(ntiles, (wg_target + nqt - 1) / nqt));
+  // the deep stage (a gathered batch of the few queries an earlier stage could
+  // not settle): as many lists as two workgroups per CU give ONE query tile, so
+  // the floors sit far behind the top (the a_M + 2B threshold keeps the wide
+  // set small)
+  // (lane lists of at most ~1 GB: nq_pad slots x 4 nsplit lists x 8 entries x 8 B)
+  if (s.deep)
+    n = std::max<int64_t>(
+        n, std::min<int64_t>({ntiles, 512, (1ll << 30) / ((int64_t)p.nq_pad * 4 * 8 * 8)}));
+  // A first pass on the bf16 plane (the adaptive order's choice when int8
+  // hands on too many: embedding-like clustered rows) takes twice the lists:
+  // its checks then settle more queries and fewer go to the deep stage
+  // (clustered C3 37.1k -> 43.0k queries/s; on uniform rows the int8 pass
+  // loses 3 % with them; profiles/r05s)
+  if (!s.gathered && !s.deep && s.plane == FILTER_BF16) n = std::min<int64_t>(ntiles, 2 * n);
+  // A small batch (at most skinny_max_q queries, the first stage of a search
+  // routed here by run_topk) streams its plane once through skinny_plane_topk
+  // instead of an x1 pass over a whole query tile: 2,048 lists of 8 per query,
+  // the deep stage's count
+  p.small = !s.gathered && !s.deep && s.nq <= s.skinny_max_q && !s.self_join &&
+            (s.mode == MODE_IP || (s.mode == MODE_L2 && s.l2aug));  // the pass's IP
+  if (p.small) n = std::min<int64_t>(512, std::max<int64_t>(1, (ntiles + 3) / 4));
+  n = std::max<int64_t>(n, 1);
+  // A/B: more (shorter) database splits = more lane lists per query
+  p.nsplit = (int)std::min<int64_t>(ntiles, n * s.split_mult);
+  return p;
+}
 
 // ---- vs_api.hip: what the search entry points share -------------------------
 // The argument checks of a search, in the order every entry point makes them:

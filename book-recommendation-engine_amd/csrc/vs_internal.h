@@ -206,6 +206,31 @@ struct BoundArgs {
   int rows_exact = 0;
 };
 BoundArgs make_bound_args(int64_t ld, int filter);
+// What the two verification launchers share (launch_verify_rescore,
+// launch_verify_wide): one stage's candidates, rows, queries and outputs.
+struct VerifyArgs {
+  int mode = MODE_IP;  // the exact keys' metric (MODE_L2D: faiss's sequential L2 formula)
+  int KF = 0;          // approximate candidates per query
+  int M = 0;           // exact entries the answer needs (the bound is checked at the M-th)
+  const void* X = nullptr;    // the index's rows: fp32 (xesize 4) or bf16 (xesize 2)
+  int xesize = 4;
+  const float* xn = nullptr;  // |x|^2 per row
+  const float* Q = nullptr;   // the stage's fp32 query rows (stride ld)
+  const float* qn = nullptr;  // the queries' aux values (|q|^2 for L2)
+  int64_t ld = 0;
+  BoundArgs ba;
+  const unsigned* stats = nullptr;  // the plane's index maxima (launch_bound_stats)
+  Partials lists;  // the filter pass's lane lists (L entries each), for their floors
+  int L = 0;
+  float* okey = nullptr;  // sorted exact lists of KP entries per query
+  int* oid = nullptr;
+  int KP = 0;
+  int* fail = nullptr;  // fail[q] = 1: the next stage must redo query q
+  const float* qinv = nullptr;   // cosine: 1/|q|
+  const float* xinv = nullptr;   // cosine: 1/|x|
+  const float* qr2i8 = nullptr;  // int8 plane: the queries' residual norms (null for bf16)
+  const float* qcut = nullptr;   // the pass's query cuts (dump launches; null: none)
+};
 // The augmentation of an L2 index's int8 plane (launch_quantize_i8_l2aug).
 struct L2Aug {
   int m = 0;          // int8 extra columns (a multiple of 64)
@@ -294,15 +319,9 @@ hipError_t launch_mul_arrays(const float* a, const float* b, int64_t n, float* o
 // keys of each query (ascending, local rows), `lists` the filter pass's lane
 // lists (L entries each) for their floors; writes sorted exact lists of KP
 // entries (okey/oid) and fail[q] = 1 where the exact engine must redo query q.
-// qsc: the queries' int8 scales (int8 filter; null for bf16).
-hipError_t launch_verify_rescore(int mode, int nq, int KF, int M, const float* Dk,
-                                 const int64_t* Ik, const void* X, const float* xn,
-                                 const float* Q, const float* qn, int64_t ld, const BoundArgs& ba,
-                                 const unsigned* stats, Partials lists, int L, float* okey,
-                                 int* oid, int KP, int* fail, hipStream_t st,
-                                 const float* qinv, const float* xinv, const float* qsc,
-                                 const int* qcount = nullptr, const float* qcut = nullptr,
-                                 int xesize = 4);
+// qcount (optional): only the queries q < *qcount (device-side count).
+hipError_t launch_verify_rescore(const VerifyArgs& v, int nq, const float* Dk, const int64_t* Ik,
+                                 const int* qcount, hipStream_t st);
 // Flagged queries (flags[i] != 0) -> ascending qlist[0 .. *count), all on the
 // device; *total += count and *total_n += n when not null.
 hipError_t launch_compact_flags(const int* flags, int n, int* list, int* count,
@@ -318,6 +337,9 @@ hipError_t launch_compact_flags(const int* flags, int n, int* list, int* count,
 // are reused instead of read again.  sizes (optional): += the wide-set entries
 // and the rescored ones.
 constexpr int kWideCap = 4096;
+hipError_t launch_verify_wide(const VerifyArgs& v, int nq_max, const int* qlist, const int* count,
+                              const float* Dk, const int64_t* Ik, unsigned long long* sizes,
+                              hipStream_t st);
 // The most candidates (KF) the verification rescores per query, and the longest
 // exact list (KP) it writes: 1024 holds inner product's 2k - 1 for k <= 512
 // (and k <= 1023 for L2 / cosine); past it the paged exact engine answers.
@@ -347,14 +369,6 @@ struct ScratchChunk {
 hipError_t scratch_chunk_get(size_t bytes, hipStream_t st, ScratchChunk* out);
 void scratch_chunk_put(const ScratchChunk& c, hipStream_t st);
 void scratch_trim();
-hipError_t launch_verify_wide(int mode, int nq_max, const int* qlist, const int* count, int KF,
-                              int M, const void* X, const float* xn, const float* Q,
-                              const float* qn, int64_t ld, const BoundArgs& ba,
-                              const unsigned* stats, Partials lists, int L, float* okey, int* oid,
-                              int KP, int* fail, hipStream_t st, const float* qinv,
-                              const float* xinv, const float* qsc, const float* Dk,
-                              const int64_t* Ik, unsigned long long* sizes = nullptr,
-                              const float* qcut = nullptr, int xesize = 4);
 // Query cuts and dump launches of the filter pass (vs_x1_cuts.hip, "Query
 // cuts"): bkey[q] = the verification's bound B of query q; x1_dump_applies:
 // the pass of this mode and plane has a dump form (launch_gemm_topk_x1 then
@@ -454,9 +468,6 @@ hipError_t launch_fill_synthetic_ids(void* out, int esize, const int64_t* ids, i
                                      int64_t d, int64_t ldo, uint64_t seed, hipStream_t st);
 // Fill n (D, I) pairs with the empty-result sentinel of `mode`.
 hipError_t launch_fill_empty(int mode, float* D, int64_t* I, int64_t n, hipStream_t st);
-// Stable compaction helper: copy the kept rows of [src0, src0+n) into tmp,
-// given the sorted removed-row list (device).  Also moves the norms.
-// Rows are `rowbytes` long (multiple of 16).
 // out[0 .. n) = 0 .. n-1 and *count = n (device): a gathered batch of every query.
 hipError_t launch_iota(int* out, int n, int* count, hipStream_t st);
 // Tombstones: rows[0 .. n) (device) filled with NaN elements and a NaN norm;
@@ -469,6 +480,9 @@ hipError_t launch_fill_nan_rows(void* X, int64_t rowbytes, float* norms, int esi
                                 float* scale = nullptr);
 hipError_t launch_label_map(int64_t* I, int64_t n, const int64_t* dead, int64_t ndead,
                             int64_t id_base, hipStream_t st);
+// Stable compaction helper: copy the kept rows of [src0, src0+n) into tmp,
+// given the sorted removed-row list (device).  Also moves the norms.
+// Rows are `rowbytes` long (multiple of 16).
 hipError_t launch_gather_kept(const void* X, const float* norms, int64_t rowbytes, int64_t src0,
                               int64_t n, const int64_t* removed, int64_t nrem, void* tmp,
                               float* tmp_norms, hipStream_t st);

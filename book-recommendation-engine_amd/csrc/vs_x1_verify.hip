@@ -233,24 +233,21 @@ __global__ __launch_bounds__(64) void verify_rescore_kernel(
   if (lane == 0) fail[q] = pass ? 0 : 1;
 }
 
-hipError_t launch_verify_rescore(int mode, int nq, int KF, int M, const float* Dk,
-                                 const int64_t* Ik, const void* X, const float* xn,
-                                 const float* Q, const float* qn, int64_t ld, const BoundArgs& ba,
-                                 const unsigned* stats, Partials lists, int L, float* okey,
-                                 int* oid, int KP, int* fail, hipStream_t st, const float* qinv,
-                                 const float* xinv, const float* qr2i8, const int* qcount,
-                                 const float* qcut, int xesize) {
-  if (KF > kVerifyMaxKF || KP > kVerifyMaxKF || KF > KP || M < 1 || M > KF || ld % 4 != 0 ||
-      L < 1 || L > lists.KP || (xesize != 4 && xesize != 2))
+hipError_t launch_verify_rescore(const VerifyArgs& v, int nq, const float* Dk, const int64_t* Ik,
+                                 const int* qcount, hipStream_t st) {
+  const int KF = v.KF;
+  if (KF > kVerifyMaxKF || v.KP > kVerifyMaxKF || KF > v.KP || v.M < 1 || v.M > KF ||
+      v.ld % 4 != 0 || v.L < 1 || v.L > v.lists.KP || (v.xesize != 4 && v.xesize != 2))
     return hipErrorInvalidValue;
   if (nq <= 0) return hipSuccess;
-#define VS_VERIFY_T(MD, NE, RT)                                                                    \
-  hipLaunchKernelGGL((verify_rescore_kernel<MD, NE, RT>), dim3(nq), dim3(64), 0, st, KF, M, Dk, Ik, \
-                     (const RT*)X, xn, Q, qn, ld, ba, stats, lists.key, lists.id, lists.P,         \
-                     lists.KP, L, okey, oid, KP, fail, qinv, xinv, qr2i8, qcount, qcut)
+#define VS_VERIFY_T(MD, NE, RT)                                                                   \
+  hipLaunchKernelGGL((verify_rescore_kernel<MD, NE, RT>), dim3(nq), dim3(64), 0, st, KF, v.M, Dk, \
+                     Ik, (const RT*)v.X, v.xn, v.Q, v.qn, v.ld, v.ba, v.stats, v.lists.key,       \
+                     v.lists.id, v.lists.P, v.lists.KP, v.L, v.okey, v.oid, v.KP, v.fail, v.qinv, \
+                     v.xinv, v.qr2i8, qcount, v.qcut)
 #define VS_VERIFY(MD, NE)                  \
   do {                                     \
-    if (xesize == 4)                       \
+    if (v.xesize == 4)                     \
       VS_VERIFY_T(MD, NE, float);          \
     else                                   \
       VS_VERIFY_T(MD, NE, uint16_t);       \
@@ -268,13 +265,13 @@ hipError_t launch_verify_rescore(int mode, int nq, int KF, int M, const float* D
     else                   \
       VS_VERIFY(MD, 16);   \
   } while (0)
-  if (mode == MODE_IP)
+  if (v.mode == MODE_IP)
     VS_VERIFY_NE(MODE_IP);
-  else if (mode == MODE_L2)
+  else if (v.mode == MODE_L2)
     VS_VERIFY_NE(MODE_L2);
-  else if (mode == MODE_L2D)
+  else if (v.mode == MODE_L2D)
     VS_VERIFY_NE(MODE_L2D);
-  else if (mode == MODE_COS && qinv && xinv)
+  else if (v.mode == MODE_COS && v.qinv && v.xinv)
     VS_VERIFY_NE(MODE_COS);
   else
     return hipErrorInvalidValue;
@@ -542,37 +539,33 @@ __global__ __launch_bounds__(256) void verify_wide_kernel(
   }
 }
 
-hipError_t launch_verify_wide(int mode, int nq_max, const int* qlist, const int* count, int KF,
-                              int M, const void* X, const float* xn, const float* Q,
-                              const float* qn, int64_t ld, const BoundArgs& ba,
-                              const unsigned* stats, Partials lists, int L, float* okey, int* oid,
-                              int KP, int* fail, hipStream_t st, const float* qinv,
-                              const float* xinv, const float* qr2i8, const float* Dk,
-                              const int64_t* Ik, unsigned long long* sizes,
-                              const float* qcut, int xesize) {
-  if (KF > KP || KP > kVerifyMaxKF || (Dk && !Ik) || M < 1 || M > KF || ld % 4 != 0 || L < 1 ||
-      L > lists.KP || (xesize != 4 && xesize != 2))
+hipError_t launch_verify_wide(const VerifyArgs& v, int nq_max, const int* qlist, const int* count,
+                              const float* Dk, const int64_t* Ik, unsigned long long* sizes,
+                              hipStream_t st) {
+  if (v.KF > v.KP || v.KP > kVerifyMaxKF || (Dk && !Ik) || v.M < 1 || v.M > v.KF ||
+      v.ld % 4 != 0 || v.L < 1 || v.L > v.lists.KP || (v.xesize != 4 && v.xesize != 2))
     return hipErrorInvalidValue;
   if (nq_max <= 0) return hipSuccess;
   const int grid = std::min(nq_max, 2048);
-#define VS_WIDE_T(MD, RT)                                                                         \
-  hipLaunchKernelGGL((verify_wide_kernel<MD, RT>), dim3(grid), dim3(256), 0, st, qlist, count, KF, \
-                     M, (const RT*)X, xn, Q, qn, ld, ba, stats, lists.key, lists.id, lists.P,     \
-                     lists.KP, L, okey, oid, KP, fail, qinv, xinv, qr2i8, Dk, Ik, sizes, qcut)
+#define VS_WIDE_T(MD, RT)                                                                        \
+  hipLaunchKernelGGL((verify_wide_kernel<MD, RT>), dim3(grid), dim3(256), 0, st, qlist, count,   \
+                     v.KF, v.M, (const RT*)v.X, v.xn, v.Q, v.qn, v.ld, v.ba, v.stats,            \
+                     v.lists.key, v.lists.id, v.lists.P, v.lists.KP, v.L, v.okey, v.oid, v.KP,   \
+                     v.fail, v.qinv, v.xinv, v.qr2i8, Dk, Ik, sizes, v.qcut)
 #define VS_WIDE(MD)             \
   do {                          \
-    if (xesize == 4)            \
+    if (v.xesize == 4)          \
       VS_WIDE_T(MD, float);     \
     else                        \
       VS_WIDE_T(MD, uint16_t);  \
   } while (0)
-  if (mode == MODE_IP)
+  if (v.mode == MODE_IP)
     VS_WIDE(MODE_IP);
-  else if (mode == MODE_L2)
+  else if (v.mode == MODE_L2)
     VS_WIDE(MODE_L2);
-  else if (mode == MODE_L2D)
+  else if (v.mode == MODE_L2D)
     VS_WIDE(MODE_L2D);
-  else if (mode == MODE_COS && qinv && xinv)
+  else if (v.mode == MODE_COS && v.qinv && v.xinv)
     VS_WIDE(MODE_COS);
   else
     return hipErrorInvalidValue;
