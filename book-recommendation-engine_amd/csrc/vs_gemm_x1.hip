@@ -107,64 +107,42 @@ constexpr int kT = 256;               // rows (and queries) per tile
 constexpr int kNbuf = 5;              // LDS images in the ring (4: -1 %, profiles/r02y)
 constexpr int kX1ChunkTiles = 64;     // database tiles per workgroup per launch
 // dump slots (candidate rows) per lane list and segment: a segment of
-// doubling data meets ~8 rows below a list's floor, a hybrid launch's dump part
-// (three times its list part) ~24, with a tail: the dump part beats the list
-// part's 8th row at least n times when at most 7 of the best 8 + n rows lie in
-// the list part, Binomial(8 + n, 1/4) <= 7: ~2e-4 per list at n = 64 (a fifth of
-// C2's queries, with 512 lists each, handed on), ~1e-8 at n = 128
+// doubling data meets ~8 rows below a list's floor, a split pass's dump launch
+// more (by the lists' own last entries alone; the cut only lowers the floor):
+// after a list launch over a quarter of the tiles, three times as many rows
+// follow, ~24 below the floor, with a tail: the dump launch beats the list
+// launch's 8th row at least n times when at most 7 of the best 8 + n rows lie
+// in the list launch's tiles, Binomial(8 + n, 1/4) <= 7: ~2e-4 per list at
+// n = 64 (a fifth of C2's queries, with 512 lists each, handed on), ~1e-8 at
+// n = 128
 constexpr int kDumpMaxR = 128;
 // The step schedule of a launch: 1 = fragment reads half a step ahead, DMA
 // pieces between the MFMAs; 2 = separate load and matrix segments.  Measured
-// per plane and launch kind (A/B builds: VS_X1_SCHED_I8 forces one for every
-// int8 launch): int8 list launches are faster on 1 (C2 390k vs 337k
-// queries/s, C4 465k vs 437k students/s), int8 dump launches on 2 (C3 70.8k
-// vs 68.9k; profiles/r04a/r04e_sched_dump_ab.txt), bf16 on 2 (clustered
+// per plane and launch kind: int8 list launches are faster on 1 (C2 390k vs
+// 337k queries/s, C4 465k vs 437k students/s), int8 dump launches on 2 (C3
+// 70.8k vs 68.9k; profiles/r04a/r04e_sched_dump_ab.txt), bf16 on 2 (clustered
 // 34.4k vs 32.5k, profiles/r03_ab_sched.txt).
-#ifndef VS_X1_SCHED_I8
-#define VS_X1_SCHED_I8 0
-#endif
-// A/B builds only (tools/build_variant.sh -DVS_X1_SEGDMA=1): the segmented
-// schedule's four LDS-DMA pieces of step s+3 issued between the MFMAs of the
-// matrix segment (one per four MFMAs) instead of in the load segment.
-#ifndef VS_X1_SEGDMA
-#define VS_X1_SEGDMA 0
-#endif
-// A hybrid launch (mostly dump tiles) takes the dump launches' schedule.
-constexpr int x1_sched(int el, bool dump, bool hyb = false) {
-  return el != FILTER_I8 ? 2 : VS_X1_SCHED_I8 ? VS_X1_SCHED_I8 : dump || hyb ? 2 : 1;
-}
+constexpr int x1_sched(int el, bool dump) { return el != FILTER_I8 || dump ? 2 : 1; }
 // The passes with a dump form: inner product on either plane (every key
 // follows from the raw sum and, for int8, the row factor the replay reads).
 // Not the cosine: its bound is relative (B ~ 2 rho, ~0.02 at d = 1536 for
-// int8), wide beside the similarity spread of high-dimensional rows, so only
-// the lists' own floors hold its dumps down, and its row factors (s_x / |x|)
+// int8), wide beside the similarity spread of high-dimensional rows, so its
+// cut lies behind the lists' own floors, and its row factors (s_x / |x|)
 // spread widely, so a launch-wide factor bound passes ~70 rows per list and
-// segment (a d = 128 self-join of Gaussian rows: 3M lists past their slots).
-// A form with the list launches' per-group bounds and exact keys before the
-// dump (built, exact) made C4 slower: 439k vs 467k students/s at 4-5
-// launches per pass (profiles/r04w/ab_c4_cosine_dump.txt).  The bf16 L2 /
-// cosine keys also need the row norms in the kernel.
-constexpr bool x1_has_dump(int mode, int el) {
-  return mode == MODE_IP || (mode == MODE_COS && el == FILTER_I8);
-}
+// segment; the bf16 L2 / cosine keys also need the row norms in the kernel.
+// An int8 cosine dump form (the folded factors in the place of s_x) stored
+// about as many rows as list launches insert: C4 440-469k vs 471k students/s
+// (profiles/r05o).
+constexpr bool x1_has_dump(int mode, int el) { return mode == MODE_IP; }
 // The dump launches on v_mfma_i32_16x16x64_i8 (template flag S16; default):
 // int8 inner-product passes (the augmented L2 among them) under the segmented
 // schedule.  The same cycles per step as the 32x32x32 form, but the chip holds
 // a higher clock on the 16x16 shape (tools/mfma_ceiling.hip).
-// List and hybrid launches, the cosine and every bf16 kernel stay on 32x32
+// List launches, the cosine and every bf16 kernel stay on 32x32
 // (the two bf16 shapes add their fp32 partial sums in different orders, so a
 // list launch and a dump launch would not give a row the same key bits).
 constexpr bool x1_has_s16(int mode, int el) {
   return mode == MODE_IP && el == FILTER_I8 && x1_sched(el, true) == 2;
-}
-// The int8 cosine's dump form (its folded factors s_x / |x| take the place of
-// s_x; key and bound as in its list launches) is used only with VS_X1_COSDUMP=1
-// (A/B; read at every search): its cut lies behind the lists' own floors, so
-// it stores about as many rows as list launches insert (C4 440-469k vs 471k
-// students/s, profiles/r05o).
-static bool x1_cos_dump_on() {
-  const char* e = getenv("VS_X1_COSDUMP");
-  return e && atoi(e) != 0;
 }
 
 __device__ __forceinline__ unsigned long long stamp_now() {
@@ -285,7 +263,7 @@ __device__ __forceinline__ float sel16(const f32x16& v, int i) {
 // slices (QG x 16 KB per step) and serves a database tile to QG workgroups;
 // slot / QG orders the splits, so with two rounds of workgroups per CU each
 // round covers its own DG / 2 splits.  Other grids: a plain dealing.
-template <int KR, int MODE, bool DUMP, int EL, bool HYB = false, bool S16 = false>
+template <int KR, int MODE, bool DUMP, int EL, bool S16 = false>
 __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     const char* __restrict__ XH, const float* __restrict__ xs, const float* __restrict__ xaux,
     const char* __restrict__ QH, const float* __restrict__ qs, const float* __restrict__ qaux,
@@ -295,8 +273,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     const float* __restrict__ xgmax, const float* __restrict__ xgmin, const float* __restrict__ qcut,
     int* __restrict__ dcount, int* __restrict__ dslot, int dR, int qskip) {
   static_assert(!DUMP || x1_has_dump(MODE, EL), "dump form");
-  static_assert(!HYB || (!DUMP && x1_has_dump(MODE, EL)), "hybrid launch");
-  static_assert(!S16 || (DUMP && !HYB && x1_has_s16(MODE, EL)), "16x16x64 form");
+  static_assert(!S16 || (DUMP && x1_has_s16(MODE, EL)), "16x16x64 form");
   // query blocks per lane: two of 32 queries, or (S16) four of 16
   constexpr int NQB = S16 ? 4 : 2;
   constexpr int NBUF = kNbuf;
@@ -351,11 +328,6 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   const int t0 = s0 + (int)((int64_t)(s1 - s0) * chunk / nchunk);
   // parts [chunk, chunk_end) of the split's nchunk (a launch usually covers one)
   const int t1 = s0 + (int)((int64_t)(s1 - s0) * chunk_end / nchunk);
-  // Hybrid launch: the first quarter of the workgroup's tiles as a list
-  // launch, the rest as a dump launch whose floor is each list's own last
-  // entry after that quarter (a top-8 list over n rows is beaten by ~8 of every
-  // next n: ~24 dumps per list, within the slots)
-  const int tsw = HYB ? t0 + (t1 - t0 + 3) / 4 : t1;
 
   int gq[NQB], selfrow[NQB];
   float qa[NQB], qsc[NQB];
@@ -376,8 +348,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   // Dump launches: the query's cut (padding queries: nothing passes) and the
   // lane list's running dump count over the search's launches.
   // dump launches keep no list (the arrays are never touched there: no
-  // registers); the epilogue's list branch is a template of its dump tag, so
-  // it must type-check in every kernel
+  // registers)
   constexpr int KL = KR;
   float lk[2][KL];
   int li[2][KL];
@@ -449,7 +420,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     // of address arithmetic and M0 saves
     // (inner product only: the bf16 L2 / cosine list kernels have no registers
     // to spare for the two lane offsets)
-    constexpr bool kSeg = x1_sched(EL, DUMP, HYB) == 2 && MODE == MODE_IP;
+    constexpr bool kSeg = x1_sched(EL, DUMP) == 2 && MODE == MODE_IP;
     const char* xstep = nullptr;
     const char* qstep = nullptr;
     uint32_t xl0 = 0, xl2 = 0;
@@ -484,11 +455,10 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         asm volatile("" ::"v"(Tq[qb]));
       }
     };
-    // the launch's (a hybrid launch: its dump part's) largest and smallest
-    // row factor
-    auto set_factor_bounds = [&](int ta) {
+    // the launch's largest and smallest row factor
+    auto set_factor_bounds = [&]() {
       const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      for (int g = 16 * ta + ln; g < 16 * t1; g += 64) {
+      for (int g = 16 * t0 + ln; g < 16 * t1; g += 64) {
         fm = fmaxf(fm, xgmax[g]);
         fn = fminf(fn, xgmin[g]);
       }
@@ -499,40 +469,9 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       }
     };
     if constexpr (DUMP && EL == FILTER_I8) {
-      set_factor_bounds(t0);
+      set_factor_bounds();
       set_Tq();
     }
-    // Hybrid launch, at the end of its list part: the lists go to memory (the
-    // replay after the launch admits the dumps into them), each list's floor
-    // for the dump part is min(cut, its last entry)
-    auto to_dump_mode = [&]() {
-      if constexpr (HYB) {
-        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const int pl1 = sp * 4 + wr * 2 + (ln >> 5);
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-          const int64_t g = (int64_t)(qt * kT + 64 * wq + 32 * qb + (ln & 31)) * P + pl1;
-          const int64_t o = g * KP;
-#pragma unroll
-          for (int e = 0; e < KR; ++e) {
-            pkey[o + e] = lk[qb][e];
-            pid[o + e] = li[qb][e];
-          }
-          for (int e = KR; e < KP; ++e) {
-            pkey[o + e] = FLT_MAX;
-            pid[o + e] = -1;
-          }
-          const float tl = fminf(qcut[gq[qb]], li[qb][KR - 1] >= 0 ? lk[qb][KR - 1] : FLT_MAX);
-          tq[qb] = gq[qb] < nqa ? tl : -FLT_MAX;
-          dc[qb] = dcount[g];
-          asm volatile("" ::"v"(tq[qb]), "v"(dc[qb]));
-        }
-        if constexpr (EL == FILTER_I8) {
-          set_factor_bounds(tsw);
-          set_Tq();
-        }
-      }
-    };
 
     AccT<EL> acc[4][2];
     // fragments of one sub-step: A (database rows) x4, B (queries) x2
@@ -689,12 +628,10 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
 #define VS_X1_COUNT(i, v) ((void)0)
 #define VS_X1_EMARK(i) ((void)0)
 #endif
-    auto epilogue = [&](int t, auto dm_tag) {
-      // dm_tag: a dump launch's epilogue (also the dump part of a hybrid one)
-      constexpr bool DM = decltype(dm_tag)::value;
+    auto epilogue = [&](int t) {
       // a block's admission limit: the list's last entry, or the floor
       auto lim = [&](int qb) -> float {
-        if constexpr (DM) return tq[qb];
+        if constexpr (DUMP) return tq[qb];
         else return lk[qb][KL - 1];
       };
       // uniform: every row of the tile exists and none is excluded
@@ -726,7 +663,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb) {
         fmx[rb] = 0.0f;
-        if constexpr (EL == FILTER_I8 && !DM) {
+        if constexpr (EL == FILTER_I8 && !DUMP) {
           const int grp = (t * kT + ((128 * wr + 32 * rb) ^ (f & 0xE0))) >> 5;  // uniform
           const float g0 = xgmax[2 * grp], g1 = xgmax[2 * grp + 1];
           fmx[rb] = (fh & 4) ? g1 : g0;
@@ -745,7 +682,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         for (int qb = 0; qb < 2; ++qb) {
           const float last = lim(qb);
           bool p;
-          if constexpr (EL == FILTER_I8 && DM) {
+          if constexpr (EL == FILTER_I8 && DUMP) {
             int amax = acc[rb][qb][0];
 #pragma unroll
             for (int r = 1; r < 16; ++r) amax = max(amax, acc[rb][qb][r]);
@@ -776,7 +713,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         asm volatile("" ::"v"(pass));
         pass = 0;
       }
-      if constexpr (DM) {
+      if constexpr (DUMP) {
         // Dump launch: every row of a block that passed whose sum clears the
         // limit (int8: above the launch's integer threshold; bf16: -sum below
         // the limit) goes to the lane list's
@@ -819,7 +756,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
                   // slot-major (slot c of every list together): the replay's
                   // threads, one per list, read their c-th slots coalesced
                   const int64_t slot = (int64_t)c * ((int64_t)nqt * kT * P) + (int64_t)gq[qb] * P + pl;
-                  if constexpr (!(VS_X1_P(256) && DUMP)) *(i32x2*)(dslot + slot * 2) = i32x2{row, sum};
+                  if constexpr (!VS_X1_P(256)) *(i32x2*)(dslot + slot * 2) = i32x2{row, sum};
                   else asm volatile("" ::"v"(slot), "v"(row), "v"(sum));
                 }
               }
@@ -846,7 +783,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       // row blocks per load group: 2 under the segmented schedule; 1 under the
       // round-2 schedule, whose next-step fragments stay live across the
       // epilogue (registers)
-      constexpr int G = x1_sched(EL, DUMP, HYB) != 1 ? 2 : 1;
+      constexpr int G = x1_sched(EL, DUMP) != 1 ? 2 : 1;
 #pragma unroll
       for (int hp = 0; hp < 4 / G; ++hp) {
         f32x4 rv[G][4];
@@ -1061,8 +998,9 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       }
     };
 
-    constexpr int kSched = x1_sched(EL, DUMP, HYB);
+    constexpr int kSched = x1_sched(EL, DUMP);
     if constexpr (kSched == 1) {
+    static_assert(EL == FILTER_I8 && !DUMP, "the round-2 schedule: int8 list launches only");
 
     // prologue: steps 0 .. D-1 in flight, retire step 0, read its first fragments
 #pragma unroll
@@ -1149,15 +1087,15 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       VS_X1_MARK1(5);
       buf = nbuf;
     };
-    // tiles [ta, tb) with the epilogue of kind DM (a hybrid launch: its list
-    // part, then its dump part — two loops, so the lists are dead in the
-    // second)
-    auto s1_tiles = [&](int ta, int tb, auto dm_tag) {
-      for (int t = ta; t < tb; ++t) {
+    // the launch's tiles (a lambda called once, not a bare loop: hipcc assigns
+    // the loop's registers differently for the bare loop, and every measurement
+    // on record is of this form's code)
+    auto s1_tiles = [&]() {
+      for (int t = t0; t < t1; ++t) {
         s1_step(std::true_type{});
         for (int k = 1; k < nksteps; ++k) s1_step(std::false_type{});
         if constexpr (!VS_X1_P(8)) {
-          epilogue(t, dm_tag);
+          epilogue(t);
         } else {
 #pragma unroll
           for (int rb = 0; rb < 4; ++rb)
@@ -1167,13 +1105,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         VS_X1_MARK1(5);
       }
     };
-    if constexpr (HYB) {
-      s1_tiles(t0, tsw, std::false_type{});
-      to_dump_mode();
-      s1_tiles(tsw, t1, std::true_type{});
-    } else {
-      s1_tiles(t0, t1, std::integral_constant<bool, DUMP>{});
-    }
+    s1_tiles();
 #undef VS_X1_MARK1
     } else {
     // Segmented schedule: every step of a wave is a LOAD segment (the step's 12
@@ -1226,24 +1158,16 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         rd(buf, 1, fa1, fb1);
       }
       __builtin_amdgcn_sched_barrier(0);
-#if !VS_X1_SEGDMA
       stage_step();
       advance_cursor();
       __builtin_amdgcn_sched_barrier(0);
       VS_X1_MARK(0);
       // this wave's pieces of step s+1 (the younger steps stay in flight)
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#else
-      VS_X1_MARK(0);
-      // this wave's pieces of step s+1; step s+2's (issued in the previous
-      // matrix segment) stay in flight
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#endif
       VS_X1_MARK(1);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       VS_X1_MARK(2);
-#if !VS_X1_SEGDMA
       if constexpr (S16) {
 #pragma unroll
         for (int b = 0; b < 8; ++b) mfma16_b(b, first_tag);
@@ -1258,75 +1182,6 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb) mfma_rb(rb, fa1, fb1);
       }
-#else
-      {
-        // step s+3's pieces into the image of step s-2 (read two barriers ago
-        // by every wave, as in the load segment's placement), one per four MFMAs
-        const uint32_t lx = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)lbuf * (2 * kStepB) +
-                                                           (uint32_t)(2 * w) * 1024u);
-        auto piece = [&](int j, uint32_t m0v, uint32_t voff, const char* sbase) {
-          if constexpr (!kSeg) {  // the bf16 L2 / cosine kernels: no step pointers
-            stage_piece(j);
-            return;
-          }
-          uint32_t keep;
-          asm volatile(
-              "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-              "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-              : "=&s"(keep)
-              : "s"(m0v), "v"(voff), "s"(sbase)
-              : "memory");
-        };
-        static_assert(kStepB == 0x4000, "piece offsets");
-        if constexpr (S16) {
-          mfma16_b(0, first_tag);
-          mfma16_b(1, first_tag);
-        } else if constexpr (first) {
-          mfma_rb_first(0, fa0, fb0);
-          mfma_rb_first(1, fa0, fb0);
-        } else {
-          mfma_rb(0, fa0, fb0);
-          mfma_rb(1, fa0, fb0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        piece(0, lx, xl0, xstep);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (S16) {
-          mfma16_b(2, first_tag);
-          mfma16_b(3, first_tag);
-        } else if constexpr (first) {
-          mfma_rb_first(2, fa0, fb0);
-          mfma_rb_first(3, fa0, fb0);
-        } else {
-          mfma_rb(2, fa0, fb0);
-          mfma_rb(3, fa0, fb0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        piece(1, lx + 0x4000u, soff, qstep);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (S16) {
-          mfma16_b(4, first_tag);
-          mfma16_b(5, first_tag);
-        } else {
-          mfma_rb(0, fa1, fb1);
-          mfma_rb(1, fa1, fb1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        piece(2, lx + 0x400u, xl2, xstep);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (S16) {
-          mfma16_b(6, first_tag);
-          mfma16_b(7, first_tag);
-        } else {
-          mfma_rb(2, fa1, fb1);
-          mfma_rb(3, fa1, fb1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        piece(3, lx + 0x4400u, soff + 1024u, qstep);
-        __builtin_amdgcn_sched_barrier(0);
-        advance_cursor();
-      }
-#endif
       __builtin_amdgcn_sched_barrier(0);
       VS_X1_MARK(3);
       __builtin_amdgcn_s_barrier();
@@ -1335,14 +1190,14 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
       VS_X1_MARK(5);
       buf = buf + 1 == NBUF ? 0 : buf + 1;
     };
-    auto seg_tiles = [&](int ta, int tb, auto dm_tag) {
-      for (int t = ta; t < tb; ++t) {
+    auto seg_tiles = [&]() {  // (a lambda called once: as s1_tiles)
+      for (int t = t0; t < t1; ++t) {
         seg_step(std::true_type{});
         for (int k = 1; k < nksteps; ++k) seg_step(std::false_type{});
         // the tile's epilogue, beside the partner's matrix segment
         if constexpr (!VS_X1_P(8)) {
           if constexpr (S16) epilogue16(t);
-          else epilogue(t, dm_tag);
+          else epilogue(t);
         } else if constexpr (S16) {
 #pragma unroll
           for (int b = 0; b < 8; ++b)
@@ -1357,13 +1212,7 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
         VS_X1_MARK(5);
       }
     };
-    if constexpr (HYB) {
-      seg_tiles(t0, tsw, std::false_type{});
-      to_dump_mode();
-      seg_tiles(tsw, t1, std::true_type{});
-    } else {
-      seg_tiles(t0, t1, std::integral_constant<bool, DUMP>{});
-    }
+    seg_tiles();
     if (!lag) __builtin_amdgcn_s_barrier();  // the lagging waves' extra one
 #undef VS_X1_MARK
     }
@@ -1396,8 +1245,6 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
   // across the main loop: registers)
   const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int pl0 = sp * 4 + wr * 2 + (S16 ? (ln >> 4) & 1 : ln >> 5);
-  // (a hybrid launch stored its lists at the switch, which every workgroup
-  // with a tile reaches: its lists are dead past it, registers)
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb) {
     const int64_t g =
@@ -1407,14 +1254,8 @@ __global__ __launch_bounds__(512, 1) void gemm_topk_x1(
     } else if constexpr (S16) {
       // lanes l and l ^ 32 hold the same count of the same list: one writes it
       if (ln < 32) dcount[g] = dc[qb];
-    } else if (DUMP || (HYB && t1 > t0)) {
+    } else if constexpr (DUMP) {
       dcount[g] = dc[qb];
-    } else if (HYB) {  // no tile: empty lists
-      const int64_t o = g * KP;
-      for (int e = 0; e < KP; ++e) {
-        pkey[o + e] = FLT_MAX;
-        pid[o + e] = -1;
-      }
     } else {
       const int64_t o = g * KP;
 #pragma unroll
@@ -1447,22 +1288,10 @@ static bool x1_group_rounds() {
   return !e || atoi(e) != 0;
 }
 
-// Hybrid first launches (env VS_X1_HYB=1, read at every search; off by
-// default): for a workgroup with at least kHybMinTiles tiles in the launch (its
-// list part, a quarter of them, then sees >= 4 tiles: 256 rows per lane list).
-// Measured against list first launches on one box (profiles/r05j): C2 348.5k
-// vs 397.6k queries/s (the single launch's replay and dump stores cost more
-// than the list epilogue they replace), C3 76.4k vs 76.7k, clustered C3 equal:
-// kept as an exact, tested alternative, not the default.
-constexpr int kHybMinTiles = 16;
 // split passes: a list launch over the first 1/8 of every workgroup's tiles
 // (x1_split_den; C2 on one box, profiles/r05m: 426k queries/s at 1/8, 416k at
 // 1/4, 410k as one list launch)
 constexpr int kX1SplitDen = 8;
-static bool x1_hybrid_on() {
-  const char* e = getenv("VS_X1_HYB");
-  return e && atoi(e) != 0;
-}
 
 // Database tiles per workgroup per launch for a pass of per_block tiles per
 // workgroup: 64, or 32 for a pass that can dump and has 128-192 tiles per
@@ -1491,20 +1320,10 @@ static int x1_chunk_tiles(int per_block, bool can_dump) {
 // workgroup) runs as TWO launches, a list launch over the first 1/den of every
 // workgroup's tiles and one dump launch over the rest, with the cut between
 // them and one replay after: the dump launch's floor is min(cut, the list's
-// last entry), so it stores a few rows per list where a hybrid launch's
-// list-only floor stored ~24.
+// last entry), so it stores a few rows per list.
 static int x1_split_den() {
   const char* e = getenv("VS_X1_SPLIT");
   return e ? std::max(0, atoi(e)) : kX1SplitDen;
-}
-// Segmented split passes (env VS_X1_SPLITSEG=1, read at every search; A/B):
-// a split pass of den = 2^m parts (m >= 2) runs its dump part as m launches
-// over parts [1, 2), [2, 4), .. [den / 2, den), a replay after each, so every
-// segment doubles the rows seen and a lane list meets ~8 rows below its floor
-// per segment however small the list launch's share (1 / den) is.
-static bool x1_split_segments(int den) {
-  const char* e = getenv("VS_X1_SPLITSEG");
-  return e && atoi(e) != 0 && den >= 4 && (den & (den - 1)) == 0;
 }
 constexpr int kSplitMinTiles = 16;
 // (default: the bf16 plane's passes only — clustered C3 +1.4 %, C3's int8
@@ -1526,7 +1345,8 @@ static int x1_first_den(int el, bool ecut) {
 // pure (the knobs above are its only other inputs): x1_launch executes it,
 // x1_pass_dumps asks it whether a pass has dump launches (vs_engines.hip allocates
 // the dump slots and cuts by that), and vs_x1_plan shows it to CPU tests.
-enum X1Kind : int { kX1List = 0, kX1Hybrid = 1, kX1Dump32 = 2, kX1Dump16 = 3 };
+// (the values are vs_x1_plan's; 1 was the hybrid launch, retired: never produced)
+enum X1Kind : int { kX1List = 0, kX1Dump32 = 2, kX1Dump16 = 3 };
 // what follows a launch, in this order (a bit mask)
 enum : int {
   kX1Replay = 1,     // x1_replay
@@ -1541,9 +1361,8 @@ struct X1Step {
 };
 struct X1Plan {
   int nparts = 1;
-  bool cutting = false;     // the first launch's lists set cuts for the rest
-  bool hyb = false;         // launch 0 is a hybrid launch
-  bool later_dump = false;  // launches c > 0 are dump launches
+  // the first launch's lists set cuts, and launches c > 0 are dump launches
+  bool cutting = false;
   std::vector<X1Step> step;
   int nlaunch() const { return (int)step.size(); }
 };
@@ -1566,13 +1385,6 @@ static X1Plan x1_plan(int per_block, bool can_dump, int el, bool ecut, bool gath
   const int den = x1_split_den();
   const bool split = dump && nchunk < 4 && den >= 2 && per_block >= kSplitMinTiles;
   p.cutting = dump && (nchunk >= 4 || split);
-  // Hybrid first launch (gemm_topk_x1<..., HYB>): a quarter of its tiles as a
-  // list launch, the rest dumping below each list's own last entry; x1_replay
-  // right after it.  It needs no cut, so a pass of fewer launches (C2: one)
-  // dumps too, its later launches as dump launches below the lists' floors.
-  const int tiles0 = (per_block + nchunk - 1) / nchunk;
-  p.hyb = dump && !split && x1_hybrid_on() && tiles0 >= kHybMinTiles;
-  p.later_dump = p.cutting || p.hyb;
   // the launches as part ranges [p0, p1) of nparts
   // Quarter-chunk list launches (env VS_X1_QUARTER=0/1/F; default: bf16 passes
   // and int8 passes with exact-key cuts): a
@@ -1585,25 +1397,18 @@ static X1Plan x1_plan(int per_block, bool can_dump, int el, bool ecut, bool gath
   const int F = x1_first_den(el, ecut);
   const bool quarter =
       p.cutting && !split && nchunk >= 4 && F >= 2 && per_block / (F * nchunk) >= 2;
-  const bool sseg = split && x1_split_segments(den);
-  int lg = 0;
-  while ((1 << lg) < den) ++lg;
   p.nparts = split ? den : quarter ? F * nchunk : nchunk;
-  const int nlaunch = sseg ? lg + 1 : split ? 2 : quarter ? nchunk + 1 : nchunk;
+  const int nlaunch = split ? 2 : quarter ? nchunk + 1 : nchunk;
   for (int c = 0; c < nlaunch; ++c) {
     X1Step s;
-    s.p0 = sseg      ? (c == 0 ? 0 : 1 << (c - 1))
-           : split   ? (c == 0 ? 0 : 1)
+    s.p0 = split     ? (c == 0 ? 0 : 1)
            : quarter ? (c == 0 ? 0 : c == 1 ? 1 : F * (c - 1))
                      : c;
-    s.p1 = sseg      ? (c == 0 ? 1 : 1 << c)
-           : split   ? (c == 0 ? 1 : den)
+    s.p1 = split     ? (c == 0 ? 1 : den)
            : quarter ? (c == 0 ? 1 : F * c)
                      : c + 1;
-    s.kind = p.later_dump && c > 0 ? kX1Dump32 : p.hyb ? kX1Hybrid : kX1List;
+    s.kind = p.cutting && c > 0 ? kX1Dump32 : kX1List;
     s.after = 0;
-    // the hybrid launch's dumps, before the cuts read the lists
-    if (p.hyb && c == 0) s.after |= kX1Replay;
     if (p.cutting && c == 0) s.after |= kX1FirstCut | (ecut ? kX1ExactCut : 0);
     // Segments of dump launches end where the data seen doubles (after
     // launches 1, 3, 7, 15, ... and the last): a dump launch's threshold is
@@ -1622,8 +1427,8 @@ static X1Plan x1_plan(int per_block, bool can_dump, int el, bool ecut, bool gath
     // 2.8k rows per query through, most of them in the later, longer segments).
     // After the last replay nothing reads a new cut but the verification,
     // which takes a_M + 2B itself.
-    if (p.later_dump && c > 0 && (sseg || ((c + 1) & c) == 0 || c + 1 == nlaunch)) {
-      const bool again = p.cutting && recut && c + 1 < nlaunch;
+    if (p.cutting && c > 0 && (((c + 1) & c) == 0 || c + 1 == nlaunch)) {
+      const bool again = recut && c + 1 < nlaunch;
       s.after |= again ? kX1ReplayCut | (ecut ? kX1ExactCut : 0) : kX1Replay;
     }
     p.step.push_back(s);
@@ -1667,19 +1472,15 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
     // launches stay outside the spans); the first launch of a pass whose later
     // launches dump is timed apart ("<name>_list")
     if (a.timing)
-      a.timing->begin(st, !(plan.later_dump && nlaunch > 1) || c > 0,
+      a.timing->begin(st, !(plan.cutting && nlaunch > 1) || c > 0,
                       (double)(s.p1 - s.p0) / plan.nparts);
     switch (s.kind == kX1Dump32 ? x1_dump_kind(MODE, EL, a.dump32) : s.kind) {
       case kX1Dump16:
         if constexpr (x1_has_s16(MODE, EL))
-          launch(gemm_topk_x1<KR, MODE, true, EL, false, true>, s, true);
+          launch(gemm_topk_x1<KR, MODE, true, EL, true>, s, true);
         break;
       case kX1Dump32:
         if constexpr (x1_has_dump(MODE, EL)) launch(gemm_topk_x1<KR, MODE, true, EL>, s, true);
-        break;
-      case kX1Hybrid:
-        if constexpr (x1_has_dump(MODE, EL))
-          launch(gemm_topk_x1<KR, MODE, false, EL, true>, s, true);
         break;
       default:
         launch(gemm_topk_x1<KR, MODE, false, EL>, s, false);
@@ -1698,11 +1499,11 @@ static hipError_t x1_launch(const X1Args& a, Partials part, hipStream_t st, int*
 
 int x1_lane_len() { return 8; }
 int x1_dump_slots() { return kDumpMaxR; }
-// (ntotal, nsplit) carry neither the plane nor the exact-key cuts: later_dump
-// does not depend on them (they only choose the quarter list launch).
+// (ntotal, nsplit) carry neither the plane nor the exact-key cuts: whether a
+// pass cuts does not depend on them (they only choose the quarter list launch).
 bool x1_pass_dumps(int ntotal, int nsplit) {
   const int ntiles = (ntotal + kT - 1) / kT;
-  return x1_plan((ntiles + nsplit - 1) / nsplit, true, FILTER_I8, false, false, 1).later_dump;
+  return x1_plan((ntiles + nsplit - 1) / nsplit, true, FILTER_I8, false, false, 1).cutting;
 }
 
 bool x1_plan_describe(int mode, int filter, int64_t ntotal, int nsplit, bool can_dump, bool ecut,
@@ -1715,7 +1516,8 @@ bool x1_plan_describe(int mode, int filter, int64_t ntotal, int nsplit, bool can
   const X1Plan plan =
       x1_plan((int)((ntiles + nsplit - 1) / nsplit), can_dump && x1_has_dump(mode, filter), filter,
               ecut && mode == MODE_IP && filter == FILTER_I8, gathered, recut);
-  out[0] = plan.nparts, out[1] = plan.cutting, out[2] = plan.hyb, out[3] = plan.later_dump;
+  // out[2] was "launch 0 is a hybrid launch" (retired): 0, so the rest keep their indices
+  out[0] = plan.nparts, out[1] = plan.cutting, out[2] = 0, out[3] = plan.cutting;
   out[4] = x1_pass_dumps((int)ntotal, nsplit);
   for (int c = 0; c < plan.nlaunch() && c < cap; ++c) {
     const X1Step& s = plan.step[c];
@@ -1768,9 +1570,7 @@ hipError_t launch_gemm_topk_x1(int mode, const X1Args& a, Partials part, hipStre
   return x1_dispatch<FILTER_BF16>(mode, a, part, st, ndispatch);
 }
 
-bool x1_dump_applies(int mode, int filter) {
-  return x1_has_dump(mode, filter) && (mode != MODE_COS || x1_cos_dump_on());
-}
+bool x1_dump_applies(int mode, int filter) { return x1_has_dump(mode, filter); }
 
 // Filter-pass candidate count: the merged approximate candidates for `need`
 // exact entries, with a margin of at least 8 (0 = not served by the filter).

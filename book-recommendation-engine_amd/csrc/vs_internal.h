@@ -179,8 +179,10 @@ int x1_lane_len();
 // histograms of dump events per lane and launch); zeros in a real build.
 hipError_t x1_stamps(unsigned long long* out, int reset);
 // Diagnostic: the launch plan of a pass (x1_plan, vs_gemm_x1.hip) in
-// vs_x1_plan's layout (include/vsearch.h); touches no device.  dump32 as in
-// X1Args.  False for arguments no pass can have.
+// vs_x1_plan's layout (include/vsearch.h: out[2] is always 0 and launch kind 1
+// is never produced, both left from a removed launch form so that readers keep
+// their indices and values); touches no device.  dump32 as in X1Args.  False
+// for arguments no pass can have.
 bool x1_plan_describe(int mode, int filter, int64_t ntotal, int nsplit, bool can_dump, bool ecut,
                       bool gathered, int recut, bool dump32, int32_t* out, int cap, int* nlaunch);
 // Writes 4*nsplit lists of part.KP entries per query (nq_pad queries), each holding
@@ -371,7 +373,8 @@ void scratch_chunk_put(const ScratchChunk& c, hipStream_t st);
 void scratch_trim();
 // Query cuts and dump launches of the filter pass (vs_x1_cuts.hip, "Query
 // cuts"): bkey[q] = the verification's bound B of query q; x1_dump_applies:
-// the pass of this mode and plane has a dump form (launch_gemm_topk_x1 then
+// the pass of this mode and plane has a dump form: inner product on either
+// plane, the augmented L2 among them, never the cosine (launch_gemm_topk_x1 then
 // sets the cuts after its first launch and dumps in the others; the host runs
 // launch_x1_replay after it, and the verification must get the same cuts).
 hipError_t launch_qbound(int mode, const float* Q, int64_t ld, const float* qn, int filter,

@@ -386,13 +386,14 @@ int vs_x1_stamps(unsigned long long* out, int reset);
  * recut: 0 one cut per pass, 1 or 2 a new cut after every replay but the last.
  * out holds 5 + 4 cap values:
  *   out[0] parts the pass cuts every workgroup's tiles into, out[1] the first
- *   launch's lists set cuts, out[2] launch 0 is a hybrid launch, out[3] the
+ *   launch's lists set cuts, out[2] always 0 (it marked a launch form that was
+ *   removed; kept so the other values keep their indices), out[3] the
  *   launches after the first are dump launches, out[4] the same question as
  *   the search asks it before allocating dump buffers (from ntotal and nsplit
  *   alone: equal to out[3] of the call with can_dump = 1, gathered = 0);
  *   then {p0, p1, kind, after} per launch, the first min(cap, *nlaunch):
- *   parts [p0, p1); kind 0 list, 1 hybrid, 2 dump on 32x32x32 MFMAs, 3 dump on
- *   16x16x64; after, a mask of what runs next in this order: 1 replay,
+ *   parts [p0, p1); kind 0 list, 2 dump on 32x32x32 MFMAs, 3 dump on
+ *   16x16x64 (1, the removed form, is never produced); after, a mask of what runs next in this order: 1 replay,
  *   2 the first cut, 4 replay and a new cut, 8 an exact-key cut.
  * *nlaunch = the pass's launches. */
 int vs_x1_plan(int mode, int filter, int64_t ntotal, int nsplit, int can_dump, int ecut,

@@ -234,23 +234,6 @@ def test_cosine_selfjoin_keeps_list_launches(lib):
 
 
 @pytest.mark.parametrize("metric", [IP, flat.METRIC_L2])
-def test_hybrid_single_launch(lib, metric, monkeypatch):
-    """A pass of one launch (C2's shape: 37 tiles per workgroup here) runs as a
-    hybrid launch (vs_gemm_x1.hip, HYB): its first quarter of tiles keeps lists
-    in registers, the rest dumps below each list's own last entry, and the
-    replay after it admits the dumps: exact on the sample, dumps made, no list
-    out of its slots, nothing left to a later stage."""
-    monkeypatch.setenv("VS_X1_CHUNK_TILES", "64")
-    monkeypatch.setenv("VS_X1_HYB", "1")  # off by default (vs_gemm_x1.hip, x1_hybrid_on)
-    monkeypatch.setenv("VS_X1_SPLIT", "0")  # a split pass would take the pass instead
-    rng = np.random.default_rng(57)
-    xb = rng.uniform(-1, 1, (N, D_)).astype(np.float32)
-    xq = rng.uniform(-1, 1, (B, D_)).astype(np.float32)
-    dumps, over, fq, ff = _search_checked(lib, xb, xq, 10, engine="i8v", metric=metric)
-    assert fq == B and dumps > 0 and over == 0 and ff == 0, (dumps, over, ff)
-
-
-@pytest.mark.parametrize("metric", [IP, flat.METRIC_L2])
 def test_split_pass(lib, metric, monkeypatch):
     """A pass of one launch (C2's shape: 37 tiles per workgroup here) as a split
     pass (VS_X1_SPLIT=4, vs_gemm_x1.hip x1_launch): a list launch over the first
@@ -266,39 +249,13 @@ def test_split_pass(lib, metric, monkeypatch):
     assert fq == B and dumps > 0 and over == 0 and ff == 0, (dumps, over, ff)
 
 
-def test_cosine_selfjoin_dump_form(lib, monkeypatch):
-    """The int8 cosine's dump form (VS_X1_COSDUMP=1: the folded factors s_x / |x|
-    in the launch-wide threshold, the same keys as its list launches) on the
-    C4-shaped self-join above: exact on the sampled students, dump launches ran."""
-    from vsearch import faiss as vfaiss
-
-    monkeypatch.setenv("VS_X1_COSDUMP", "1")
-    rng = np.random.default_rng(14)
-    x = rng.standard_normal((N, D_)).astype(np.float32)
-    index = vfaiss.IndexFlatIP(D_)
-    index.add(x)
-    lib.filter_stats(reset=True)
-    S, I = index.selfjoin(15)
-    dumps, over = lib.filter_dump_stats()
-    lib.filter_stats(reset=True)
-    assert dumps > 0
-    rows = np.array(sorted({r for c in range(0, N, 65536) for r in (c, c + 1, c + 65535)
-                            if r < N} | set(range(0, N, N // 200))))
-    Sr, Ir = flat.pgvector_cosine_topk(x, 15, q_rows=rows)
-    bad = flat.selfjoin_mismatches(S[rows], I[rows], Sr, Ir, x, rows, strict=True)
-    assert not bad, bad[:5]
-
-
-@pytest.mark.parametrize("den,seg", [(8, "0"), (16, "1"), (32, "1")])
-def test_split_pass_segments(lib, monkeypatch, den, seg):
-    """Split passes (one launch per workgroup's tiles: 300,000 rows, 37 tiles
-    per split at the default 64-tile launches): a list launch over 1/den of
-    the tiles, then one dump launch, or (VS_X1_SPLITSEG=1) dump launches over
-    doubling part ranges with a replay after each.  Strict on the sample, no
-    list out of slots, nothing handed to the next stage."""
+def test_split_pass_eighth(lib, monkeypatch):
+    """The split pass at the default den = 8 (one launch per workgroup's tiles:
+    300,000 rows, 37 tiles per split at the default 64-tile launches): a list
+    launch over 1/8 of the tiles, then one dump launch and one replay.  Strict
+    on the sample, no list out of slots, nothing handed to the next stage."""
     monkeypatch.setenv("VS_X1_CHUNK_TILES", "64")
-    monkeypatch.setenv("VS_X1_SPLIT", str(den))
-    monkeypatch.setenv("VS_X1_SPLITSEG", seg)
+    monkeypatch.setenv("VS_X1_SPLIT", "8")
     rng = np.random.default_rng(17)
     xb = rng.uniform(-1, 1, (N, D_)).astype(np.float32)
     xq = rng.uniform(-1, 1, (B, D_)).astype(np.float32)

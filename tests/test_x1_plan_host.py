@@ -14,18 +14,17 @@ import pytest
 from vsearch import _lib
 
 IP, I8, BF16 = 0, 1, 0
-LIST, HYB, DUMP32, DUMP16 = 0, 1, 2, 3
+LIST, DUMP32, DUMP16 = 0, 2, 3  # kind 1 (the retired hybrid launch) is never produced
 REPLAY, FIRST_CUT, REPLAY_CUT, EXACT_CUT = 1, 2, 4, 8
 CAP = 704  # VS_X1_CHUNK_TILES >= 4 and 700 tiles: at most 176 launches
-KNOBS = ("VS_X1_CHUNK_TILES", "VS_X1_SPLIT", "VS_X1_SPLITSEG", "VS_X1_HYB", "VS_X1_QUARTER",
-         "VS_X1_DUMP_MFMA")
+KNOBS = ("VS_X1_CHUNK_TILES", "VS_X1_SPLIT", "VS_X1_QUARTER", "VS_X1_DUMP_MFMA")
 
 _out = (ctypes.c_int32 * (5 + 4 * CAP))()
 _n = ctypes.c_int(0)
 
 
 def plan(per_block, can_dump=1, plane=I8, ecut=0, gathered=0, recut=1, nsplit=1):
-    """(nparts, cutting, hyb, later_dump, pass_dumps, [(p0, p1, kind, after), ...]) of a
+    """(nparts, cutting, 0, later_dump, pass_dumps, [(p0, p1, kind, after), ...]) of a
     pass of per_block tiles per workgroup."""
     ntotal = 256 * per_block * nsplit
     rc = _lib.load().vs_x1_plan(IP, plane, ntotal, nsplit, can_dump, ecut, gathered, recut, _out,
@@ -45,6 +44,8 @@ def set_knobs(monkeypatch, **kw):
             monkeypatch.setenv("VS_X1_" + k, str(v))
 
 
+# Every knob value against every (can_dump, ecut) the search can ask for; None
+# is "not set" on a knob axis and "not asked for" on the other two.
 SWEEP = list(itertools.product((None, 4, 8, 64), (None, 0, 4, 8), (None, 1), (None, 1),
                                (None, 0, 1, 8)))
 
@@ -58,24 +59,25 @@ def raw_plan(per_block, can_dump, plane, ecut, gathered=0):
     return v[:5], v[5::4], v[6::4], v[7::4], v[8::4]
 
 
-@pytest.mark.parametrize("chunk,split,splitseg,hyb,quarter", SWEEP)
-def test_plan_invariants(monkeypatch, chunk, split, splitseg, hyb, quarter):
-    set_knobs(monkeypatch, CHUNK_TILES=chunk, SPLIT=split, SPLITSEG=splitseg, HYB=hyb,
-              QUARTER=quarter)
+@pytest.mark.parametrize("chunk,split,can_dump,ecut,quarter", SWEEP)
+def test_plan_invariants(monkeypatch, chunk, split, can_dump, ecut, quarter):
+    set_knobs(monkeypatch, CHUNK_TILES=chunk, SPLIT=split, QUARTER=quarter)
+    can_dump, ecut = can_dump or 0, ecut or 0
     for per_block in range(1, 701):
         # what the search asks before it allocates dump buffers (x1_pass_dumps)
         want_dumps = raw_plan(per_block, 1, I8, 0)[0][3]
-        for can_dump, plane, ecut in itertools.product((0, 1), (I8, BF16), (0, 1)):
+        for plane in (I8, BF16):
             head, p0s, p1s, kinds, after = raw_plan(per_block, can_dump, plane, ecut)
-            nparts, cutting, is_hyb, later_dump, pass_dumps = head
+            nparts, cutting, unused, later_dump, pass_dumps = head
             ctx = (per_block, can_dump, plane, ecut, head, p0s, p1s, kinds, after)
+            assert unused == 0, ctx  # was "launch 0 is a hybrid launch"
             # contiguous, non-empty ranges covering [0, nparts) once
             assert p0s[0] == 0 and p1s[-1] == nparts and p0s[1:] == p1s[:-1], ctx
             assert all(map(operator.lt, p0s, p1s)), ctx
-            # launch 0 lists (or is the hybrid launch); the later ones are all dump
-            # launches of one form, or all list launches
+            # launch 0 lists; the later ones are all dump launches of one form, or
+            # all list launches
             rest = set(kinds[1:])
-            assert kinds[0] == (HYB if is_hyb else LIST), ctx
+            assert kinds[0] == LIST, ctx
             if later_dump:
                 assert rest in (set(), {DUMP16}, {DUMP32}), ctx
             else:
@@ -86,12 +88,12 @@ def test_plan_invariants(monkeypatch, chunk, split, splitseg, hyb, quarter):
             if can_dump:
                 assert later_dump == pass_dumps, ctx
             else:
-                assert not later_dump and not is_hyb and not cutting and not any(after), ctx
+                assert not later_dump and not cutting and not any(after), ctx
             assert not cutting or later_dump, ctx
-            # after launch 0: the hybrid launch's replay, then the first cut of a
-            # cutting pass (no cut before it), an exact cut with it only when asked for
+            # after launch 0: the first cut of a cutting pass (no replay: launch 0
+            # dumps nothing), an exact cut with it only when asked for
             ex = EXACT_CUT if ecut and plane == I8 else 0
-            assert after[0] == (REPLAY if is_hyb else 0) | (FIRST_CUT | ex if cutting else 0), ctx
+            assert after[0] == (FIRST_CUT | ex if cutting else 0), ctx
             # after a dump launch: nothing, a replay, or (cutting passes) a replay and
             # a new cut, with its exact cut exactly when asked for
             allowed = {0} if not later_dump else {0, REPLAY, REPLAY_CUT | ex} if cutting \
@@ -156,11 +158,6 @@ EXACT = [
     (dict(), 150, 1, 0, (4, 1, 0, 1),
      [(0, 1, LIST, FIRST_CUT), (1, 2, D, RC), (2, 3, D, 0), (3, 4, D, REPLAY)]),
     (dict(), 150, 0, 0, (3, 0, 0, 0), [(0, 1, LIST, 0), (1, 2, LIST, 0), (2, 3, LIST, 0)]),
-    # segmented split pass
-    (dict(SPLIT=8, SPLITSEG=1), 40, 1, 0, (8, 1, 0, 1),
-     [(0, 1, LIST, FIRST_CUT), (1, 2, D, RC), (2, 4, D, RC), (4, 8, D, REPLAY)]),
-    # one hybrid launch
-    (dict(HYB=1, SPLIT=0), 61, 1, 0, (1, 0, 1, 1), [(0, 1, HYB, REPLAY)]),
 ]
 
 

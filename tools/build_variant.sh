@@ -1,7 +1,6 @@
 #!/bin/bash
 # Builds an A/B variant of libvsearch.so with extra -D flags on vs_gemm_x1.hip
-# (VS_X1_PROBE, VS_X1_STAMP, VS_X1_SCHED_I8, VS_X1_SEGDMA: the filter pass's
-# other units read none):
+# (VS_X1_PROBE, VS_X1_STAMP: the filter pass's other units read neither):
 #   tools/build_variant.sh <suffix> [-DNAME=VAL ...]  ->  vsearch/libvsearch_<suffix>.so
 #   X1_SRC=<file> tools/build_variant.sh <suffix> ...  (another vs_gemm_x1.hip, e.g.
 #   `git show HEAD~1:...` saved to a file, for before/after A/B; it must fit
