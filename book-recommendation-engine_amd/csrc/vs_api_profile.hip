@@ -286,18 +286,38 @@ int check_profiles(const char* what, const int64_t* offs, const int64_t* labels,
 
 }  // namespace
 
+namespace vs {
+namespace host {
+
+int check_excl_lists(const char* what, const int64_t* excl_offs, const int64_t* excl_labels,
+                     int64_t n) {
+  if (!excl_offs) return VS_OK;
+  if (!csr_offsets_ok(excl_offs, n))
+    return fail(VS_E_INVALID, std::string(what) + ": offsets must start at 0 and not decrease");
+  if (excl_offs[n] > 0 && !excl_labels)
+    return fail(VS_E_INVALID, std::string(what) + ": null exclusion labels");
+  return VS_OK;
+}
+
+int search_excl_held(vs_index* idx, const float* x, int64_t n, int64_t k, const int64_t* excl_offs,
+                     const int64_t* excl_labels, float* D, int64_t* I, int flags, hipStream_t st) {
+  ExclSets es;
+  if (excl_offs && excl_offs[n] > 0)
+    build_excl_sets(idx, n, excl_offs, excl_labels, nullptr, nullptr, &es);
+  return search_excl_locked(idx, x, n, k, &es, D, I, flags, st);
+}
+
+}  // namespace host
+}  // namespace vs
+
 extern "C" {
 
 int vs_search_excl(vs_index* idx, const float* x, int64_t n, int64_t k, const int64_t* excl_offs,
                    const int64_t* excl_labels, float* D, int64_t* I, int flags, void* stream) {
   const int rc = check_search_args("vs_search_excl", idx, &n, k);  // buffers: after the offsets
   if (rc) return rc;
-  if (excl_offs) {
-    if (!csr_offsets_ok(excl_offs, n))
-      return fail(VS_E_INVALID, "vs_search_excl: offsets must start at 0 and not decrease");
-    if (excl_offs[n] > 0 && !excl_labels)
-      return fail(VS_E_INVALID, "vs_search_excl: null exclusion labels");
-  }
+  const int rcl = check_excl_lists("vs_search_excl", excl_offs, excl_labels, n);
+  if (rcl) return rcl;
   // no list holds a label: vs_search itself
   if (!excl_offs || excl_offs[n] == 0) return vs_search(idx, x, n, k, D, I, flags, stream);
   if (!x || !D || !I) return fail(VS_E_INVALID, "vs_search_excl: null buffer");
@@ -341,12 +361,8 @@ int vs_search_profiles(vs_index* idx, const int64_t* offs, const int64_t* labels
   const int rc0 = check_profiles("vs_search_profiles", offs, labels, weights, n);
   if (rc0) return rc0;
   if (n == 0) return VS_OK;
-  if (excl_offs) {
-    if (!csr_offsets_ok(excl_offs, n))
-      return fail(VS_E_INVALID, "vs_search_profiles: offsets must start at 0 and not decrease");
-    if (excl_offs[n] > 0 && !excl_labels)
-      return fail(VS_E_INVALID, "vs_search_profiles: null exclusion labels");
-  }
+  const int rcl = check_excl_lists("vs_search_profiles", excl_offs, excl_labels, n);
+  if (rcl) return rcl;
   if (!D || !I) return fail(VS_E_INVALID, "vs_search_profiles: null buffer");
   hipStream_t st = (hipStream_t)stream;
   std::shared_lock<std::shared_mutex> lk(idx->mu);

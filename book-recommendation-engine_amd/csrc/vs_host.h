@@ -527,5 +527,15 @@ int search_staged(const char* what, vs_index* idx, const float* x, int64_t n, in
   return out.finish(what, st);
 }
 
+// ---- vs_api_profile.hip: for the entry points built on vs_search_excl --------
+// vs_search_excl's checks of its lists ("<what>: ..."; null offsets: no lists).
+int check_excl_lists(const char* what, const int64_t* excl_offs, const int64_t* excl_labels,
+                     int64_t n);
+// vs_search / vs_search_excl (lists null or all empty: the plain search) for a
+// caller that holds the reader lock, the device and a reader mark on `st`, its
+// arguments checked.
+int search_excl_held(vs_index* idx, const float* x, int64_t n, int64_t k, const int64_t* excl_offs,
+                     const int64_t* excl_labels, float* D, int64_t* I, int flags, hipStream_t st);
+
 }  // namespace host
 }  // namespace vs

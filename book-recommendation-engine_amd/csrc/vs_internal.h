@@ -597,4 +597,26 @@ hipError_t launch_mean_rows(const void* X, int esize, int64_t ld, int d, const i
                             const int64_t* rows, const float* wts, const float* W, int64_t nq,
                             float* out, hipStream_t st);
 
+// MMR searches (vs_mmr.hip; vs_api_mmr.hip vs_mmr_select / vs_search_mmr).
+// The longest candidate list of a query: the staged engine's candidate limit.
+constexpr int kMmrMaxFetch = 1024;
+// rows[i] = the row in place of candidate label labels[i] (id_base applied; the
+// sorted dead list skipped), -1 for the empty slot -1.  Any other label that is
+// not one of the `live` labels also gives -1 and sets *bad to 1 (bad may be null).
+hipError_t launch_mmr_rows(const int64_t* labels, int64_t n, const int64_t* dead, int64_t ndead,
+                           int64_t id_base, int64_t live, int64_t* rows, int* bad, hipStream_t st);
+// S[q][i] = cos(Q[q], row rows[q][i]) and NN[q][i] = |row|^2 in fp64 (fixed
+// summation order, the unit's header) for nq <= 65535 queries (Q: fp32, stride
+// d) of F <= kMmrMaxFetch candidates each; an empty slot: S = 0, NN = -1.
+hipError_t launch_mmr_sims(const void* X, int esize, int64_t ld, int d, const float* Q,
+                           const int64_t* rows, int nq, int F, double* S, double* NN,
+                           hipStream_t st);
+// The greedy MMR selection over S / NN: pos[q][0 .. k) = the picks' positions
+// in pick order, -1 past min(k, candidates).  Dout != null: also the picks'
+// entries of Dc / Ic ([q][F]) into Dout / Iout ([q][k]), padded with (pad, -1).
+hipError_t launch_mmr_pick(const void* X, int esize, int64_t ld, const int64_t* rows, int nq,
+                           int F, int k, double lambda, const double* S, const double* NN,
+                           int* pos, const float* Dc, const int64_t* Ic, float pad, float* Dout,
+                           int64_t* Iout, hipStream_t st);
+
 }  // namespace vs

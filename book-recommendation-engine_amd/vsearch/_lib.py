@@ -68,6 +68,10 @@ SIGNATURES = {
     "vs_mean_rows": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_int, _vp]),
     "vs_search_profiles": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
                                     _vp, _c_int, _vp]),
+    "vs_mmr_select": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_double, _vp, _c_int,
+                               _vp]),
+    "vs_search_mmr": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, ctypes.c_double, _vp, _vp, _vp,
+                               _vp, _c_int, _vp]),
     "vs_range_search": (_c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_float, _c_int, _vp,
                                  ctypes.POINTER(_vp)]),
     "vs_range_size": (_c_int, [_vp, _i64p, _i64p]),

@@ -26,6 +26,10 @@ not vendored) that the reference reaches through LangChain's ``FAISS`` store:
   candidate path (reconstruct the rated books, weighted mean, search, drop the
   books already read: candidate_builder.py:138-203) for many students in one
   call, every query with its own exclusion list
+* ``index.search_mmr(x, k, fetch_k, lambda_mult)`` and ``index.mmr_select`` —
+  LangChain's maximal-marginal-relevance re-rank of the ``fetch_k`` nearest
+  rows (``FAISS.max_marginal_relevance_search*``), on the device instead of
+  ``fetch_k`` reconstructs and a Python loop per query
 
 Argument checks mirror faiss's python wrapper (``assert d == self.d``,
 ``assert k > 0``); library failures raise ``RuntimeError`` subclasses.
@@ -64,6 +68,7 @@ __all__ = [
     "selector_bitmap",
     "exclusion_csr",
     "profile_csr",
+    "gather_picks",
     "normalize_L2",
     "read_index",
     "write_index",
@@ -261,6 +266,23 @@ def profile_csr(profiles):
     weights = np.concatenate(wts) if n else np.zeros(0, dtype=np.float32)
     return (offs, np.ascontiguousarray(labels, dtype=np.int64),
             np.ascontiguousarray(weights, dtype=np.float32))
+
+
+def gather_picks(D, I, pos, metric: int):
+    """The entries of a search's (D, I) at the positions ``pos`` (``mmr_select``'s
+    result; -1 = no pick) as (D float32, I int64) of pos's shape, padded the way
+    a search pads: (+FLT_MAX for L2 | -FLT_MAX for inner product, -1)."""
+    D = np.asarray(D, dtype=np.float32)
+    I = np.asarray(I, dtype=np.int64)
+    pos = np.asarray(pos)
+    fmax = np.finfo(np.float32).max
+    pad = np.float32(fmax if metric == METRIC_L2 else -fmax)
+    if D.shape[1] == 0:
+        return (np.full(pos.shape, pad, dtype=np.float32), np.full(pos.shape, -1, dtype=np.int64))
+    safe = np.where(pos >= 0, pos, 0).astype(np.int64)
+    Dp = np.where(pos >= 0, np.take_along_axis(D, safe, axis=1), pad).astype(np.float32)
+    Ip = np.where(pos >= 0, np.take_along_axis(I, safe, axis=1), -1).astype(np.int64)
+    return Dp, Ip
 
 
 def _ptr(a: np.ndarray):
@@ -581,6 +603,73 @@ class IndexFlat(Index):
             D.ctypes.data, I.ctypes.data, _lib.RAW_ORDER if raw else 0, None),
             "vs_search_profiles")
         return D, I
+
+    def mmr_select(self, x, cand_labels, k, lambda_mult: float = 0.5) -> np.ndarray:
+        """LangChain's ``maximal_marginal_relevance`` over stored rows, on the
+        device: ``cand_labels`` (int64 (n, fetch_k), -1 = an empty slot that
+        keeps its position) are query i's candidates, and row i of the result
+        (int32 (n, k)) holds the positions into that list of the min(k,
+        candidates) picks in pick order, -1 after them.  Cosines and scores
+        are fp64 (include/vsearch.h, "MMR searches").  A label the index does
+        not hold raises RuntimeError."""
+        x = _as_f32_rows(x, self._d)
+        n = x.shape[0]
+        cand = np.ascontiguousarray(cand_labels, dtype=np.int64)
+        if cand.ndim != 2 or cand.shape[0] != n:
+            raise ValueError(f"cand_labels: expected shape ({n}, fetch_k), got {cand.shape}")
+        k = int(k)
+        assert k > 0
+        pos = np.empty((n, k), dtype=np.int32)
+        if n == 0:
+            return pos
+        if cand.shape[1] == 0:
+            pos.fill(-1)
+            return pos
+        _lib.check(self._lib.vs_mmr_select(self._h, x.ctypes.data, n, cand.ctypes.data,
+                                           cand.shape[1], k, float(lambda_mult), pos.ctypes.data,
+                                           0, None), "vs_mmr_select")
+        return pos
+
+    def search_mmr(self, x, k, fetch_k: int = 20, lambda_mult: float = 0.5, *, params=None,
+                   exclude=None):
+        """``search(x, fetch_k)`` re-ranked by maximal marginal relevance, the
+        candidates staying on the device: returns (D float32 (n, k), I int64
+        (n, k)), the picks' faiss scores and labels in pick order, padded with
+        label -1 after min(k, candidates).  ``exclude`` as in ``search``; with
+        ``params=SearchParameters(sel=...)`` the candidates come from the
+        selector search and ``mmr_select`` re-ranks them (not both)."""
+        x = _as_f32_rows(x, self._d)
+        n = x.shape[0]
+        k = int(k)
+        fetch_k = int(fetch_k)
+        assert k > 0 and fetch_k > 0
+        sel = getattr(params, "sel", None) if params is not None else None
+        if sel is not None:
+            if exclude is not None:
+                raise ValueError("search_mmr: pass exclude or params.sel, not both")
+            Dc, Ic = self.search(x, fetch_k, params=params)
+            return gather_picks(Dc, Ic, self.mmr_select(x, Ic, k, lambda_mult),
+                                self._metric)
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        if n == 0:
+            return D, I
+        offs, labels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+        _lib.check(self._lib.vs_search_mmr(
+            self._h, x.ctypes.data, n, k, fetch_k, float(lambda_mult),
+            offs.ctypes.data if offs is not None else None,
+            _ptr(labels) if labels is not None else None, D.ctypes.data, I.ctypes.data, 0, None),
+            "vs_search_mmr")
+        return D, I
+
+    def search_mmr_device(self, xq_ptr: int, n: int, k: int, fetch_k: int, lambda_mult: float,
+                          D_ptr: int, I_ptr: int, stream: int = 0) -> None:
+        """``search_mmr`` with every buffer on this index's device,
+        stream-ordered on `stream`."""
+        _lib.check(self._lib.vs_search_mmr(
+            self._h, ctypes.c_void_p(xq_ptr), int(n), int(k), int(fetch_k), float(lambda_mult),
+            None, None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+            _lib.IN_DEVICE | _lib.OUT_DEVICE, ctypes.c_void_p(stream)), "vs_search_mmr")
 
     # queries per vs_range_search call (the C-ABI's limit); larger batches are
     # searched in chunks and the parts concatenated

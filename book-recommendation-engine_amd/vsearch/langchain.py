@@ -17,6 +17,11 @@ types and error behaviour:
   fetch_k)``, skip label -1, docstore lookup, optional metadata filter and
   ``score_threshold`` (``<=`` for L2, ``>=`` for inner product), ``docs[:k]``;
   the score is faiss's D value (squared L2 / inner product) as ``np.float32``.
+* ``max_marginal_relevance_search[_by_vector]`` /
+  ``max_marginal_relevance_search_with_score_by_vector`` — LangChain's
+  signatures and defaults (``k=4, fetch_k=20, lambda_mult=0.5, filter=None``);
+  ``maximal_marginal_relevance`` as recalled (langchain is not vendored), the
+  re-rank on the device (``index.search_mmr`` / ``index.mmr_select``).
 * ``delete`` — ``ValueError`` for unknown ids, then ``index.remove_ids`` and
   contiguous renumbering of ``index_to_docstore_id``.
 * ``save_local`` / ``load_local`` — ``index.faiss`` in faiss's flat binary
@@ -594,6 +599,80 @@ class FAISS:
             out.append(row)
         return out
 
+    # -- MMR searches -----------------------------------------------------------------------
+    def max_marginal_relevance_search_with_score_by_vector(
+            self, embedding: List[float], *, k: int = 4, fetch_k: int = 20,
+            lambda_mult: float = 0.5, filter: Optional[Any] = None,
+            exact_filter: bool = False) -> List[Tuple[Document, float]]:
+        """LangChain's MMR search: the `fetch_k` nearest documents re-ranked by
+        maximal marginal relevance (each pick trades its cosine to the query
+        against its largest cosine to the picks before it, weighted by
+        `lambda_mult`: 1 = relevance only, 0 = diversity only), the first k
+        picks returned in pick order.  The score of a document is the faiss
+        score of the search (squared L2 / inner product), not the MMR score.
+        The re-rank runs on the device (``index.search_mmr``), where LangChain
+        reconstructs every candidate and loops in Python.
+
+        With `filter`, LangChain's behaviour: search ``fetch_k * 2``, filter on
+        the host, re-rank what is left (``index.mmr_select``).
+        ``exact_filter=True`` makes the filter a selector instead: exactly
+        min(fetch_k, matches) candidates are re-ranked."""
+        vector = np.array([embedding], dtype=np.float32)
+        if self._normalize_L2:
+            vfaiss.normalize_L2(vector)
+        if filter is None:
+            scores, labels = self.index.search_mmr(vector, k, fetch_k, lambda_mult)
+            return self._docs_of_row(scores[0], labels[0])
+        if exact_filter:
+            scores, labels = self.index.search_mmr(
+                vector, k, fetch_k, lambda_mult,
+                params=vfaiss.SearchParameters(sel=self._filter_selector(filter)))
+            return self._docs_of_row(scores[0], labels[0])
+        scores, labels = self.index.search(vector, fetch_k * 2)
+        filter_func = _create_filter_func(filter)
+        kept = []
+        for s, i in zip(scores[0], labels[0]):
+            if i == -1:
+                continue
+            _id = self.index_to_docstore_id[int(i)]
+            doc = self.docstore.search(_id)
+            if not isinstance(doc, Document):
+                raise ValueError(f"Could not find document for id {_id}, got {doc}")
+            if filter_func(doc.metadata):
+                kept.append((doc, s, int(i)))
+        if not kept:
+            return []
+        cand = np.array([[i for _, _, i in kept]], dtype=np.int64)
+        pos = self.index.mmr_select(vector, cand, k, lambda_mult)
+        return [(kept[p][0], kept[p][1]) for p in pos[0] if p >= 0]
+
+    def max_marginal_relevance_search_by_vector(self, embedding: List[float], k: int = 4,
+                                                fetch_k: int = 20, lambda_mult: float = 0.5,
+                                                filter: Optional[Any] = None,
+                                                **kwargs: Any) -> List[Document]:
+        return [d for d, _ in self.max_marginal_relevance_search_with_score_by_vector(
+            embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, filter=filter,
+            exact_filter=bool(kwargs.get("exact_filter", False)))]
+
+    def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20,
+                                      lambda_mult: float = 0.5, filter: Optional[Any] = None,
+                                      **kwargs: Any) -> List[Document]:
+        return self.max_marginal_relevance_search_by_vector(
+            self._embed_query(query), k=k, fetch_k=fetch_k, lambda_mult=lambda_mult,
+            filter=filter, **kwargs)
+
+    def max_marginal_relevance_search_batch_by_vector(self, embeddings, k: int = 4,
+                                                      fetch_k: int = 20,
+                                                      lambda_mult: float = 0.5):
+        """Batched variant (one engine call for many queries, library-specific
+        like ``similarity_search_batch_by_vector``): a list of [(Document,
+        score)] per query."""
+        vec = np.array(embeddings, dtype=np.float32)
+        if self._normalize_L2:
+            vfaiss.normalize_L2(vec)
+        scores, labels = self.index.search_mmr(vec, k, fetch_k, lambda_mult)
+        return [self._docs_of_row(scores[q], labels[q]) for q in range(vec.shape[0])]
+
     # -- profile searches -------------------------------------------------------------------
     def _key_labels(self, field: str) -> Dict[Any, List[int]]:
         """metadata[field] -> labels holding it, ascending.  Built once per
@@ -645,7 +724,9 @@ class FAISS:
         return kept, rows, lists
 
     def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
-                               key: str = "book_id") -> List[List[Tuple[Document, float]]]:
+                               key: str = "book_id",
+                               mmr: Optional[Tuple[int, float]] = None
+                               ) -> List[List[Tuple[Document, float]]]:
         """The reference's per-student candidate path
         (candidate_builder.py:138-203) for many students in one device call.
         Each profile is a list of ``(metadata[key] value, weight)`` — a
@@ -658,7 +739,13 @@ class FAISS:
         fewer when most of them were read.  A profile none of whose keys are
         in the store gets ``[]``, as the reference returns, and takes no part
         in the device call.  Library-specific: LangChain's store has no
-        counterpart."""
+        counterpart.
+
+        ``mmr=(fetch_k, lambda_mult)`` re-ranks every profile's `fetch_k`
+        nearest allowed documents by maximal marginal relevance on the device
+        (``index.search_mmr`` over the same mean queries and exclusions) and
+        returns the first k picks in pick order, so a recommendation list does
+        not fill with near-copies of one book."""
         profiles = list(profiles)
         if exclude is not None:
             exclude = list(exclude)
@@ -667,7 +754,14 @@ class FAISS:
         kept, rows, lists = self.profile_requests(profiles, exclude, key)
         if not kept:
             return out
-        if self._normalize_L2:  # the store normalises every query it searches
+        if mmr is not None:
+            fetch_k, lambda_mult = mmr
+            vec = self.index.mean_rows(rows)
+            if self._normalize_L2:
+                vfaiss.normalize_L2(vec)
+            scores, labels = self.index.search_mmr(vec, k, int(fetch_k), float(lambda_mult),
+                                                   exclude=lists)
+        elif self._normalize_L2:  # the store normalises every query it searches
             vec = self.index.mean_rows(rows)
             vfaiss.normalize_L2(vec)
             scores, labels = self.index.search(vec, k, exclude=lists)

@@ -23,6 +23,9 @@ HBM and serves the same vector-store calls to any number of clients:
   row (op ``search`` with ``exclude``), and ``recommend_for_profiles`` takes a
   student's weighted-mean query and the books they have read into the same
   stacked batch as everyone else's (``index.search(x, k, exclude=...)``).
+* MMR requests (``max_marginal_relevance_search*``, ``recommend_for_profiles``
+  with ``mmr=``) run on their own, as ``exact_filter`` requests do: their
+  re-rank is part of the engine call (``index.search_mmr``).
 * ``RemoteFAISS(address, authkey)`` is the client: the LangChain ``FAISS`` read /
   write surface the reference's call sites use, plus ``.index.ntotal/.d/.search``.
 * Access: the HMAC auth key has no default (the caller supplies a secret);
@@ -255,7 +258,11 @@ class IndexService:
         return {"search_batches": self._coalescer.batches, "search_rows": self._coalescer.rows}
 
     def _accept_loop(self):
-        while not self._closed.is_set():
+        # the flag is looked at only after accept() returns: close() wakes this
+        # thread with a throwaway connection, whose handshake needs it in
+        # accept() (a loop that left on the flag alone, between two accepts,
+        # left close() waiting for that handshake for ever)
+        while True:
             try:
                 conn = self._listener.accept()
             except Exception:  # noqa: BLE001 - bad auth or listener closed
@@ -338,7 +345,27 @@ class IndexService:
             else:
                 vec = self._vectors(h, payload)
             return {"results": self._search_docs(vec, h)}, b""
+        if op == "max_marginal_relevance_search":
+            if "query" in h:
+                vec = np.asarray([st._embed_query(h["query"])], dtype=np.float32)
+            else:
+                vec = self._vectors(h, payload)
+            # an MMR request runs on its own, as an exact_filter one does: the
+            # coalescer stacks plain searches that share one k
+            docs = self._read(st.max_marginal_relevance_search_with_score_by_vector, vec[0],
+                              k=int(h.get("k", 4)), fetch_k=int(h.get("fetch_k", 20)),
+                              lambda_mult=float(h.get("lambda_mult", 0.5)),
+                              filter=h.get("filter"), exact_filter=bool(h.get("exact_filter")))
+            return {"results": [[d.to_json(), float(s)] for d, s in docs]}, b""
         if op == "recommend_for_profiles":
+            if h.get("mmr") is not None:  # on its own too
+                fetch_k, lambda_mult = h["mmr"]
+                profiles = [[(v, float(w)) for v, w in p] for p in h["profiles"]]
+                rows = self._read(st.recommend_for_profiles, profiles, int(h.get("k", 4)),
+                                  exclude=h.get("exclude"), key=h.get("key", "book_id"),
+                                  mmr=(int(fetch_k), float(lambda_mult)))
+                return {"results": [[[d.to_json(), float(s)] for d, s in row]
+                                    for row in rows]}, b""
             return {"results": self._recommend(h)}, b""
         if op == "embed_query":
             return {"vector": [float(v) for v in st._embed_query(h["query"])]}, b""
@@ -527,13 +554,40 @@ class RemoteFAISS:
         return [d for d, _ in self.similarity_search_with_score(
             query, k, filter=filter, fetch_k=fetch_k, exact_filter=exact_filter, **kwargs)]
 
-    def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
-                               key: str = "book_id") -> List[List[Tuple[Document, np.float32]]]:
+    def max_marginal_relevance_search_with_score_by_vector(
+            self, embedding, *, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
+            filter=None, exact_filter: bool = False):
+        v = np.ascontiguousarray(np.asarray([embedding], dtype=np.float32))
+        return self._search({"op": "max_marginal_relevance_search", "k": int(k),
+                             "fetch_k": int(fetch_k), "lambda_mult": float(lambda_mult),
+                             "filter": filter, "exact_filter": bool(exact_filter),
+                             "shape": list(v.shape)}, v.astype("<f4").tobytes())
+
+    def max_marginal_relevance_search_by_vector(self, embedding, k: int = 4, fetch_k: int = 20,
+                                                lambda_mult: float = 0.5, filter=None,
+                                                **kwargs) -> List[Document]:
+        return [d for d, _ in self.max_marginal_relevance_search_with_score_by_vector(
+            embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, filter=filter,
+            exact_filter=bool(kwargs.get("exact_filter", False)))]
+
+    def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20,
+                                      lambda_mult: float = 0.5, filter=None,
+                                      **kwargs) -> List[Document]:
+        return [d for d, _ in self._search(
+            {"op": "max_marginal_relevance_search", "query": query, "k": int(k),
+             "fetch_k": int(fetch_k), "lambda_mult": float(lambda_mult), "filter": filter,
+             "exact_filter": bool(kwargs.get("exact_filter", False))})]
+
+    def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None, key: str = "book_id",
+                               mmr: Optional[Tuple[int, float]] = None
+                               ) -> List[List[Tuple[Document, np.float32]]]:
         """``FAISS.recommend_for_profiles`` on the server; concurrent callers
-        share one engine batch."""
+        share one engine batch (a request with ``mmr=`` runs on its own)."""
         header = {"op": "recommend_for_profiles", "k": int(k), "key": key,
                   "profiles": [[[v, float(w)] for v, w in p] for p in profiles],
                   "exclude": None if exclude is None else [list(e) for e in exclude]}
+        if mmr is not None:  # (without it the frame is what it always was)
+            header["mmr"] = [int(mmr[0]), float(mmr[1])]
         res = self._call(header)[0]["results"]
         return [[(Document.from_json(d), np.float32(s)) for d, s in row] for row in res]
 

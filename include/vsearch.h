@@ -260,6 +260,67 @@ int vs_search_profiles(vs_index* idx, const int64_t* offs, const int64_t* labels
                        const int64_t* excl_labels, int exclude_profile, float* D, int64_t* I,
                        int flags, void* stream);
 
+/* ---- MMR searches ----------------------------------------------------------
+ * LangChain's maximal-marginal-relevance searches
+ * (FAISS.max_marginal_relevance_search*, as_retriever(search_type="mmr")):
+ * search fetch_k rows, then pick k of them greedily, each pick trading its
+ * similarity to the query against its similarity to the picks before it.  The
+ * reference appends a second row when a book is re-ingested
+ * (src/incremental_workers/book_vector/main.py:148), so a plain top-k can
+ * return one book twice, and its cooldown logic exists "to improve
+ * recommendation diversity" (src/recommendation_api/service.py:1104, 1398).
+ * LangChain re-ranks on the host (reconstruct every candidate, numpy cosine
+ * matrices, a Python loop per query); here the candidates stay in HBM.
+ *
+ * The definition is langchain_community.vectorstores.utils
+ * maximal_marginal_relevance / cosine_similarity (0.3.x) as recalled:
+ * langchain is not vendored.  For one query q and its candidate list
+ * c_0 .. c_{F-1} (stored rows by label; -1 is an empty slot, no candidate, but
+ * it keeps its position):
+ *   cos(a, b) = dot(a, b) / sqrt(dot(a, a) * dot(b, b)), every dot product a
+ *   sum in fp64 of the exact products of the fp32 values (bf16 indexes: the
+ *   stored value widened to fp32, as vs_reconstruct_n returns it; the query is
+ *   never rounded); a non-finite quotient (a zero-norm row or query) counts as 0.
+ *   With s_i = cos(q, c_i): the first pick is the candidate with the largest
+ *   s_i; each later pick maximises
+ *     lambda_mult * s_i - (1 - lambda_mult) * max_{j picked} cos(c_i, c_j)
+ *   over the candidates not yet picked, evaluated in fp64; ties go to the
+ *   lowest position (LangChain compares with strict > in list order); the
+ *   selection stops after min(k, candidates) picks.
+ * The summation order inside a dot product is the kernel's own but fixed (no
+ * atomics, no dependence on a candidate's position or on the batch): results
+ * are bit-identical from run to run and equal rows get equal scores.  Not
+ * promised: which of two candidates wins when their scores differ by less
+ * than the rounding of those sums, (4d + 16) * 2^-53.
+ *
+ * Both calls check, before the index is read and in this order: the index,
+ * n >= 0, k > 0, fetch_k > 0, lambda_mult finite, the buffers (VS_E_INVALID);
+ * fetch_k > 1024 is VS_E_UNSUPPORTED (the staged engine's candidate limit;
+ * callers re-rank longer lists in pieces).  k > fetch_k is legal, n == 0 is
+ * success.  The re-rank's scratch stays within 64 MiB per chunk of queries.
+ *
+ * vs_mmr_select: the positions (into each query's candidate list) chosen by
+ * MMR, in pick order.  cand: n * fetch_k int64 labels (id_base applied as
+ * everywhere), -1 allowed anywhere, a duplicate label simply a duplicate
+ * candidate; any other label that is not a live label: VS_E_INVALID (faiss
+ * reconstruct throws).  pos: n * k int32, -1 past min(k, candidates).
+ * VS_IN_DEVICE covers x and cand (the call then waits for `stream` to read
+ * one validity flag), VS_OUT_DEVICE covers pos. */
+int vs_mmr_select(vs_index* idx, const float* x, int64_t n, const int64_t* cand, int64_t fetch_k,
+                  int64_t k, double lambda_mult, int32_t* pos, int flags, void* stream);
+/* vs_search / vs_search_excl for fetch_k, then the selection: D, I = the chosen
+ * entries' faiss scores and labels in pick order, padded (+-FLT_MAX, -1).  The
+ * candidate order is exactly what vs_search / vs_search_excl return for
+ * k = fetch_k (inner product: faiss's tie order); fetch_k past the live rows
+ * pads, and the padding slots are empty slots.  excl_offs / excl_labels as
+ * vs_search_excl (NULL: none).  VS_IN_DEVICE applies to x, VS_OUT_DEVICE to D
+ * and I; the stream contract is vs_search_excl's.  The candidates never leave
+ * the device (n * fetch_k scores and labels of scratch, as a search with
+ * device outputs holds).  Callers: FAISS.max_marginal_relevance_search*. */
+int vs_search_mmr(vs_index* idx, const float* x, int64_t n, int64_t k, int64_t fetch_k,
+                  double lambda_mult, const int64_t* excl_offs, const int64_t* excl_labels,
+                  float* D, int64_t* I, int flags, void* stream);
+
 /* ---- range search ----------------------------------------------------------
  * faiss IndexFlat::range_search(n, x, radius, result[, params.sel]): every row
  * within the radius, as many as there are — strict comparisons as faiss, L2:
