@@ -537,11 +537,15 @@ hipError_t launch_gemv_topk_rows(int KP, int mode, int nq, const void* X, int es
 // rows.  fill = true, with off = the exclusive scan of cnt (nq_pad * nsplit + 1
 // entries): the candidates' rows, ascending, at cand[off[q * nsplit + split] ..);
 // nothing is written outside a segment, and *err = 1 if a segment does not
-// come out as counted.
+// come out as counted.  MODE_COS (the range self-join): Q = the stored rows
+// from the first query row on, qaux / xaux = 1/|row| (qaux from that row on),
+// key -(ip * (qaux[q] * xaux[row])).  upper_q0 >= 0 (MODE_COS only; the first
+// query's row): query tile t reads the row tiles from the one that holds row
+// upper_q0 + t * kBQ on, and its splits divide that range.
 hipError_t launch_gemm_range(bool fill, int mode, const void* X, const float* xaux, const void* Q,
                              const float* qaux, int64_t ld, int esize, int ntotal, int nq_pad,
                              int nsplit, const float* thr, int* cnt, const int64_t* off,
-                             int* cand, int* err, hipStream_t st);
+                             int* cand, int* err, hipStream_t st, int64_t upper_q0 = -1);
 // out[0] = bits of the largest non-NaN norm of rows [0, n), out[1] = out[2] = 0
 // (the `stats` of launch_qbound with BoundArgs::rows_exact); part = scratch of
 // range_norm_max_parts() entries.
@@ -549,9 +553,10 @@ int range_norm_max_parts();
 hipError_t launch_range_norm_max(const float* norms, int64_t n, unsigned* part, unsigned* out,
                                  hipStream_t st);
 // thr[q] = radkey + bkey[q] rounded up for q < nq (NaN radkey: NaN; a bound
-// that is NaN: +inf), NaN for the padding queries [nq, nq_pad).
+// that is NaN: +inf), NaN for the padding queries [nq, nq_pad).  bstride = 0:
+// bkey[0] is every query's bound.
 hipError_t launch_range_thr(const double* bkey, int nq, int nq_pad, float radkey, float* thr,
-                            hipStream_t st);
+                            hipStream_t st, int bstride = 1);
 // off[0 .. n] = the exclusive scan of cnt[0 .. n) (off[n] = the total).
 hipError_t launch_range_scan(const int* cnt, int64_t n, int64_t* off, hipStream_t st);
 // Candidate c of query q (off[q * nsplit] <= c < off[(q + 1) * nsplit]):
@@ -563,6 +568,16 @@ hipError_t launch_range_verify(int mode, const int* cand, int64_t total, const i
                                const float* Q, const float* qn, int64_t ld, int ntotal,
                                float radius, const uint32_t* rbits, float* ekey, uint8_t* flag,
                                hipStream_t st);
+// The range self-join's verification: query q is row q0 + q of X, candidate c
+// as above; ekey[c] = the exact cosine (fp64 sum of the two stored rows'
+// products, exact_key<MODE_COS> with rinv = 1/|row| on both sides), flag[c] =
+// ekey[c] >= min_sim and the row is not the query's (exclude_self) / comes
+// after it (upper).
+hipError_t launch_range_join_verify(const int* cand, int64_t total, const int64_t* off, int nsplit,
+                                    int nq, const void* X, int xesize, const float* rinv,
+                                    int64_t ld, int ntotal, int64_t q0, float min_sim,
+                                    int exclude_self, int upper, float* ekey, uint8_t* flag,
+                                    hipStream_t st);
 // hits[q] = the flags set among query q's candidates.
 hipError_t launch_range_hits(const uint8_t* flag, const int64_t* off, int nsplit, int nq,
                              int* hits, hipStream_t st);

@@ -5,6 +5,8 @@
 // error bound), in two passes that take identical decisions — one counts, a
 // scan turns the counts into offsets, one fills — and the verification decides
 // every candidate by the rescoring's exact key (vs_x1_device.h exact_key).
+// The range self-join (vs_range_selfjoin, "Range self-join") runs the same
+// passes with the stored rows as queries and the cosine key.
 #include <algorithm>
 #include <cmath>
 
@@ -30,12 +32,23 @@ namespace vs {
 // candidates are contiguous and ascending.  Both passes run the same
 // arithmetic on the same grid; should they ever disagree, the fill pass writes
 // nothing outside its segment and raises *err (the host fails the call).
-template <int MODE, typename T, bool FILL>
+//
+// MODE_COS (the range self-join): Q is the index's own rows, read in place from
+// the call's first query row, qaux / xaux their inverse norms, and the key is
+// gemm_topk's cosine expression.  UPPER (a query reports only the rows after
+// it): query tile qt starts its row tiles at the one that holds its first
+// query row, row qrow0 + qt * kBQ, and its splits divide that range — a row
+// tile wholly below the diagonal is never loaded; both passes derive the range
+// from this one expression.  The rows r <= q of the tiles on the diagonal are
+// left to the verification.
+template <int MODE, typename T, bool FILL, bool UPPER = false>
 __global__ __launch_bounds__(256, 2) void gemm_range(
     const T* __restrict__ X, const float* __restrict__ xaux, const T* __restrict__ Q,
     const float* __restrict__ qaux, int64_t ld, int nstage, int ntotal, int ntiles, int nsplit,
     int nqt, const float* __restrict__ thr, int* __restrict__ cnt,
-    const int64_t* __restrict__ off, int* __restrict__ cand, int* __restrict__ err) {
+    const int64_t* __restrict__ off, int* __restrict__ cand, int* __restrict__ err,
+    int qrow0) {
+  static_assert(!UPPER || MODE == MODE_COS, "the triangle is the self-join's");
   static_assert(sizeof(T) == 4 || sizeof(T) == 2, "fp32 or bf16 rows");
   // [buf][X|Q][128 rows][128 B]; viewed as floats (32 per row) for addressing.
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * kBN * kBK];
@@ -56,13 +69,21 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
   }
   const int qt = lb % nqt;
   const int sp = lb / nqt;
-  const int t0 = (int)((int64_t)sp * ntiles / nsplit);
-  const int t1 = (int)((int64_t)(sp + 1) * ntiles / nsplit);
+  int t0, t1;
+  if constexpr (UPPER) {
+    const int tlo = min((qrow0 + qt * kBQ) / kBN, ntiles);
+    const int nt = ntiles - tlo;
+    t0 = tlo + (int)((int64_t)sp * nt / nsplit);
+    t1 = tlo + (int)((int64_t)(sp + 1) * nt / nsplit);
+  } else {
+    t0 = (int)((int64_t)sp * ntiles / nsplit);
+    t1 = (int)((int64_t)(sp + 1) * ntiles / nsplit);
+  }
 
   const int qloc = 32 * w + c32;
   const int gq = qt * kBQ + qloc;
   float qa = 0.0f;
-  if constexpr (MODE == MODE_L2) qa = qaux[gq];
+  if constexpr (MODE == MODE_L2 || MODE == MODE_COS) qa = qaux[gq];
   const float th = thr[gq];
   const int64_t seg = (int64_t)gq * nsplit + sp;
   int64_t base = 0, end = 0;
@@ -157,14 +178,15 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
       for (int j = 0; j < 4; ++j) {
         const int rb = r0 + 32 * s + 8 * j + 4 * h;
         f32x4 xa = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (MODE == MODE_L2) xa = *(const f32x4*)(xaux + rb);
+        if constexpr (MODE == MODE_L2 || MODE == MODE_COS) xa = *(const f32x4*)(xaux + rb);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int row = rb + i;
           const float v = acc[s][j * 4 + i];
           float key;
           if constexpr (MODE == MODE_IP) key = -v;
-          else key = l2_from_ip(qa, xa[i], v);
+          else if constexpr (MODE == MODE_L2) key = l2_from_ip(qa, xa[i], v);
+          else key = -(v * (qa * xa[i]));
           const bool hit = row < ntotal && key <= th;  // a NaN key or threshold: no
           m |= (uint32_t)hit << (j * 4 + i);
         }
@@ -199,19 +221,20 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
   }
 }
 
-template <int MODE>
+template <int MODE, bool UPPER = false>
 static hipError_t gemm_range_mode(bool fill, const void* X, const float* xaux, const void* Q,
                                   const float* qaux, int64_t ld, int esize, int ntotal,
                                   int nq_pad, int nsplit, const float* thr, int* cnt,
-                                  const int64_t* off, int* cand, int* err, hipStream_t st) {
+                                  const int64_t* off, int* cand, int* err, hipStream_t st,
+                                  int qrow0 = 0) {
   const int ntiles = (ntotal + kBN - 1) / kBN;
   const int nqt = nq_pad / kBQ;
   const int nblk = nqt * nsplit;
   const int nstage = (int)(ld * esize / 128);
 #define VS_RANGE_GO(T, FILL)                                                                   \
-  hipLaunchKernelGGL((gemm_range<MODE, T, FILL>), dim3(nblk), dim3(256), 0, st, (const T*)X,   \
-                     xaux, (const T*)Q, qaux, ld, nstage, ntotal, ntiles, nsplit, nqt, thr, cnt, \
-                     off, cand, err)
+  hipLaunchKernelGGL((gemm_range<MODE, T, FILL, UPPER>), dim3(nblk), dim3(256), 0, st,         \
+                     (const T*)X, xaux, (const T*)Q, qaux, ld, nstage, ntotal, ntiles, nsplit, \
+                     nqt, thr, cnt, off, cand, err, qrow0)
   if (esize == 4) {
     if (fill) VS_RANGE_GO(float, true);
     else VS_RANGE_GO(float, false);
@@ -226,16 +249,25 @@ static hipError_t gemm_range_mode(bool fill, const void* X, const float* xaux, c
 hipError_t launch_gemm_range(bool fill, int mode, const void* X, const float* xaux, const void* Q,
                              const float* qaux, int64_t ld, int esize, int ntotal, int nq_pad,
                              int nsplit, const float* thr, int* cnt, const int64_t* off,
-                             int* cand, int* err, hipStream_t st) {
+                             int* cand, int* err, hipStream_t st, int64_t upper_q0) {
   if (nq_pad <= 0 || nq_pad % kBQ != 0 || (ld * esize) % 128 != 0 || (esize != 4 && esize != 2) ||
       ntotal <= 0 || nsplit < 1 || !thr || (fill ? (!off || !cand || !err) : !cnt))
     return hipErrorInvalidValue;
+  if (upper_q0 >= 0 && mode != MODE_COS) return hipErrorInvalidValue;
   if (mode == MODE_IP)
     return gemm_range_mode<MODE_IP>(fill, X, xaux, Q, qaux, ld, esize, ntotal, nq_pad, nsplit, thr,
                                     cnt, off, cand, err, st);
   if (mode == MODE_L2)
     return gemm_range_mode<MODE_L2>(fill, X, xaux, Q, qaux, ld, esize, ntotal, nq_pad, nsplit, thr,
                                     cnt, off, cand, err, st);
+  if (mode == MODE_COS) {
+    if (!xaux || !qaux || upper_q0 >= ntotal) return hipErrorInvalidValue;
+    if (upper_q0 >= 0)
+      return gemm_range_mode<MODE_COS, true>(fill, X, xaux, Q, qaux, ld, esize, ntotal, nq_pad,
+                                             nsplit, thr, cnt, off, cand, err, st, (int)upper_q0);
+    return gemm_range_mode<MODE_COS>(fill, X, xaux, Q, qaux, ld, esize, ntotal, nq_pad, nsplit,
+                                     thr, cnt, off, cand, err, st);
+  }
   return hipErrorInvalidValue;
 }
 
@@ -293,15 +325,16 @@ hipError_t launch_range_norm_max(const float* norms, int64_t n, unsigned* part, 
 // thr[q] = the radius key + B_q rounded up (a row whose exact key passes the
 // radius has its GEMM key within B_q of it, so at or below thr[q]).  A NaN
 // radius admits nothing (NaN); a bound that is not finite admits every row
-// with a key (+inf); padding queries admit nothing.
+// with a key (+inf); padding queries admit nothing.  bstride = 0: one bound
+// for every query (the self-join's cosine bound is a constant).
 __global__ __launch_bounds__(256) void range_thr_kernel(const double* __restrict__ bkey, int nq,
                                                         int nq_pad, float radkey,
-                                                        float* __restrict__ thr) {
+                                                        float* __restrict__ thr, int bstride) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= nq_pad) return;
   float t = __builtin_nanf("");
   if (q < nq && radkey == radkey) {
-    const double tp = (double)radkey + bkey[q];
+    const double tp = (double)radkey + bkey[(int64_t)q * bstride];
     if (tp == tp) {
       t = (float)tp;
       if ((double)t < tp) t = nextafterf(t, INFINITY);
@@ -313,10 +346,11 @@ __global__ __launch_bounds__(256) void range_thr_kernel(const double* __restrict
 }
 
 hipError_t launch_range_thr(const double* bkey, int nq, int nq_pad, float radkey, float* thr,
-                            hipStream_t st) {
-  if (nq < 0 || nq_pad < nq || nq_pad <= 0) return hipErrorInvalidValue;
+                            hipStream_t st, int bstride) {
+  if (nq < 0 || nq_pad < nq || nq_pad <= 0 || (bstride != 0 && bstride != 1))
+    return hipErrorInvalidValue;
   hipLaunchKernelGGL(range_thr_kernel, dim3((nq_pad + 255) / 256), dim3(256), 0, st, bkey, nq,
-                     nq_pad, radkey, thr);
+                     nq_pad, radkey, thr, bstride);
   return hipGetLastError();
 }
 
@@ -429,6 +463,84 @@ hipError_t launch_range_verify(int mode, const int* cand, int64_t total, const i
     return hipErrorInvalidValue;
 #undef VS_RV
 #undef VS_RV_T
+  return hipGetLastError();
+}
+
+// The self-join's verification (MODE_COS): one wave per candidate, both
+// operands stored rows (fp32 x fp32, or bf16 x bf16 widened exactly), summed in
+// wave_dot's order.  Every product of two stored values is exact in fp64 and
+// commutes, and exact_key<MODE_COS> multiplies the two inverse norms with each
+// other first, so the key of (a, b) is the key of (b, a) bit for bit.  Query q
+// is row q0 + q; a candidate is a hit iff sim >= min_sim (not strict: the
+// comparison of vs_selfjoin's min_sim; NaN never passes) and the row is not
+// the query's own (exclude_self) / comes after it (upper).
+template <typename RT>
+__device__ __forceinline__ double wave_dot_rows(const RT* __restrict__ x, const RT* __restrict__ y,
+                                                int64_t ld, int lane) {
+  double acc = 0.0;
+  for (int64_t c = lane * 4; c < ld; c += 256) {
+    const f32x4 xv = row4(x + c);
+    const f32x4 yv = row4(y + c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc = fma((double)xv[e], (double)yv[e], acc);
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  return acc;
+}
+
+template <typename RT>
+__global__ __launch_bounds__(256) void range_join_verify_kernel(
+    const int* __restrict__ cand, int64_t total, const int64_t* __restrict__ off, int nsplit,
+    int nq, const RT* __restrict__ X, const float* __restrict__ rinv, int64_t ld, int ntotal,
+    int q0, float min_sim, int exclude_self, int upper, float* __restrict__ ekey,
+    uint8_t* __restrict__ flag) {
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= total) return;
+  int lo = 0, hi = nq - 1;  // the last query whose segment starts at or before c
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[(int64_t)mid * nsplit] <= c) lo = mid;
+    else hi = mid - 1;
+  }
+  const int qr = q0 + lo;
+  const int r = cand[c];
+  bool live = r >= 0 && r < ntotal;
+  if (exclude_self) live = live && r != qr;
+  if (upper) live = live && r > qr;
+  if (!live) {  // wave-uniform
+    if (lane == 0) {
+      ekey[c] = 0.0f;
+      flag[c] = 0;
+    }
+    return;
+  }
+  const double acc = wave_dot_rows<RT>(X + (int64_t)r * ld, X + (int64_t)qr * ld, ld, lane);
+  const float sim = -exact_key<MODE_COS>((float)acc, qr, r, nullptr, nullptr, rinv, rinv);
+  if (lane == 0) {
+    ekey[c] = sim;
+    flag[c] = sim >= min_sim ? 1 : 0;  // NaN (a zero row, a NaN threshold): no
+  }
+}
+
+hipError_t launch_range_join_verify(const int* cand, int64_t total, const int64_t* off, int nsplit,
+                                    int nq, const void* X, int xesize, const float* rinv,
+                                    int64_t ld, int ntotal, int64_t q0, float min_sim,
+                                    int exclude_self, int upper, float* ekey, uint8_t* flag,
+                                    hipStream_t st) {
+  if (total <= 0) return hipSuccess;
+  if (nq < 1 || nsplit < 1 || ld % 4 != 0 || (xesize != 4 && xesize != 2) || total > INT_MAX ||
+      !rinv || q0 < 0 || q0 + nq > ntotal)
+    return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)((total + 3) / 4);
+  if (xesize == 4)
+    hipLaunchKernelGGL(range_join_verify_kernel<float>, dim3(blocks), dim3(256), 0, st, cand, total,
+                       off, nsplit, nq, (const float*)X, rinv, ld, ntotal, (int)q0, min_sim,
+                       exclude_self, upper, ekey, flag);
+  else
+    hipLaunchKernelGGL(range_join_verify_kernel<uint16_t>, dim3(blocks), dim3(256), 0, st, cand,
+                       total, off, nsplit, nq, (const uint16_t*)X, rinv, ld, ntotal, (int)q0,
+                       min_sim, exclude_self, upper, ekey, flag);
   return hipGetLastError();
 }
 

@@ -84,6 +84,8 @@ SIGNATURES = {
         _c_int,
         [_vp, _c_i64, _c_i64, _c_i64, _c_int, ctypes.c_float, _vp, _vp, _c_int, _vp],
     ),
+    "vs_range_selfjoin": (_c_int, [_vp, _c_i64, _c_i64, ctypes.c_float, _c_int, _c_int, _c_int, _vp,
+                                   ctypes.POINTER(_vp)]),
     "vs_merge_topk": (
         _c_int,
         [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _vp],

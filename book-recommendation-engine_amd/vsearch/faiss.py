@@ -21,6 +21,9 @@ not vendored) that the reference reaches through LangChain's ``FAISS`` store:
 * ``index.range_search(x, thresh)`` — every row within a radius, in place of
   the reference's thresholds applied after a k-bounded search
   (graph_refresher/main.py:339-354, mcp_book_server.py:818-896)
+* ``index.range_selfjoin(min_sim)`` — every stored pair at or above a cosine
+  threshold (the student graph without its ``LIMIT 15``,
+  graph_refresher/main.py:339-354)
 * ``index.search(x, k, exclude=...)``, ``index.mean_rows(profiles)`` and
   ``index.search_profiles(profiles, k)`` — the reference's per-student
   candidate path (reconstruct the rated books, weighted mean, search, drop the
@@ -675,13 +678,9 @@ class IndexFlat(Index):
     # searched in chunks and the parts concatenated
     _RANGE_CHUNK = 65536
 
-    def _range_call(self, x, thresh, sel_handle):
-        """One vs_range_search call: (lims int64 (n+1), D, I) as numpy arrays."""
-        n = x.shape[0]
-        h = ctypes.c_void_p()
-        _lib.check(self._lib.vs_range_search(self._h, sel_handle, x.ctypes.data, n,
-                                             ctypes.c_float(thresh), 0, None, ctypes.byref(h)),
-                   "vs_range_search")
+    def _range_take(self, h):
+        """Copies a vs_range handle out as (lims int64 (nq+1), D, I) numpy
+        arrays and destroys it."""
         try:
             nq = ctypes.c_int64(0)
             total = ctypes.c_int64(0)
@@ -696,6 +695,39 @@ class IndexFlat(Index):
                        "vs_range_copy")
         finally:
             self._lib.vs_range_destroy(h)
+        return lims, D, I
+
+    def _range_call(self, x, thresh, sel_handle):
+        """One vs_range_search call: (lims int64 (n+1), D, I) as numpy arrays."""
+        n = x.shape[0]
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.vs_range_search(self._h, sel_handle, x.ctypes.data, n,
+                                             ctypes.c_float(thresh), 0, None, ctypes.byref(h)),
+                   "vs_range_search")
+        return self._range_take(h)
+
+    def _range_join_call(self, q0, nq, min_sim, exclude_self, upper):
+        """One vs_range_selfjoin call: (lims int64 (nq+1), S, I) as numpy arrays."""
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.vs_range_selfjoin(self._h, int(q0), int(nq), ctypes.c_float(min_sim),
+                                               1 if exclude_self else 0, 1 if upper else 0, 0,
+                                               None, ctypes.byref(h)),
+                   "vs_range_selfjoin")
+        return self._range_take(h)
+
+    @staticmethod
+    def _range_concat(parts, n):
+        """The (lims, D, I) parts of consecutive query chunks as one result of n
+        queries: lims uint64 (n+1), D, I."""
+        lims = np.zeros(n + 1, dtype=np.uint64)
+        base, q0 = 0, 0
+        for pl, _, _ in parts:
+            m = len(pl) - 1
+            lims[q0 + 1:q0 + m + 1] = (pl[1:] + base).astype(np.uint64)
+            base += int(pl[-1])
+            q0 += m
+        D = np.concatenate([p[1] for p in parts]) if len(parts) > 1 else parts[0][1]
+        I = np.concatenate([p[2] for p in parts]) if len(parts) > 1 else parts[0][2]
         return lims, D, I
 
     def range_search(self, x, thresh, *, params=None):
@@ -730,16 +762,7 @@ class IndexFlat(Index):
         finally:
             if owned:
                 handle.close()
-        lims = np.zeros(n + 1, dtype=np.uint64)
-        base, q0 = 0, 0
-        for pl, _, _ in parts:
-            m = len(pl) - 1
-            lims[q0 + 1:q0 + m + 1] = (pl[1:] + base).astype(np.uint64)
-            base += int(pl[-1])
-            q0 += m
-        D = np.concatenate([p[1] for p in parts]) if len(parts) > 1 else parts[0][1]
-        I = np.concatenate([p[2] for p in parts]) if len(parts) > 1 else parts[0][2]
-        return lims, D, I
+        return self._range_concat(parts, n)
 
     def search_device(self, xq_ptr: int, n: int, k: int, D_ptr: int, I_ptr: int,
                       stream: int = 0, raw: bool = False, selector=None) -> None:
@@ -797,6 +820,34 @@ class IndexFlat(Index):
                                          ctypes.c_float(min_sim), S.ctypes.data, I.ctypes.data,
                                          0, None), "vs_selfjoin")
         return S, I
+
+    def range_selfjoin(self, min_sim, *, q0: int = 0, nq: int | None = None,
+                       exclude_self: bool = True, upper: bool = False, chunk: int = 65536):
+        """Cosine range self-join over stored rows [q0, q0+nq): every row whose
+        similarity with the query row is >= ``min_sim``, as many as there are
+        (``selfjoin`` without its k).  Returns (lims uint64 (nq+1), S float32,
+        I int64): row q0 + i's hits are S[lims[i]:lims[i+1]] /
+        I[lims[i]:lims[i+1]], in ascending label order.
+
+        Every pair is decided by its exact key, which is the same bits for
+        (a, b) and (b, a): the full join is symmetric.  ``upper=True`` keeps, for
+        each query row q, only the rows r > q — each unordered pair once, for
+        about half the work — whether or not ``exclude_self`` is set (a row is
+        never after itself).  Zero-norm rows and a NaN ``min_sim`` match
+        nothing.  One C call per ``chunk`` query rows (at most 65536)."""
+        q0 = int(q0)
+        nq = self.ntotal - q0 if nq is None else int(nq)
+        chunk = int(chunk)
+        assert 0 < chunk <= 65536
+        min_sim = float(min_sim)
+        if nq <= 0:
+            if nq < 0:
+                raise ValueError("range_selfjoin: query rows out of range")
+            return (np.zeros(1, dtype=np.uint64), np.empty(0, dtype=np.float32),
+                    np.empty(0, dtype=np.int64))
+        parts = [self._range_join_call(q0 + c0, min(chunk, nq - c0), min_sim, exclude_self, upper)
+                 for c0 in range(0, nq, chunk)]
+        return self._range_concat(parts, nq)
 
     def selfjoin_device(self, k: int, q0: int, nq: int, D_ptr: int, I_ptr: int, *,
                         exclude_self: bool = True, min_sim: float = -np.inf,

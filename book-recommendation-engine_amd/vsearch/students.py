@@ -14,6 +14,13 @@ top-k), with the %.6f quantisation applied on the host exactly as the text
 round-trip does.  Output rows are the ``student_similarity(a, b, sim)`` tuples
 (sql/00_init_schema.sql:105-111) the refresher would insert.
 
+The graph itself is a threshold graph — every pair with ``sim >= threshold``;
+the ``LIMIT 15`` is there because SQL needs a k, and in a dense cluster it drops
+every neighbour past the 15th.  ``student_edges`` / ``StudentIndex.edges`` /
+``StudentIndex.edges_of`` answer that question directly: one range self-join
+(``vs_range_selfjoin``), as many rows as pass.  The top-15 forms above remain
+the drop-in replacement.
+
 Semantics notes: ties (equal similarity) are ordered by lower row; SQL leaves
 them unspecified.  Zero-norm vectors never match; pgvector returns NaN for them
 and the refresher's ``sim >= threshold`` test drops NaN too.
@@ -69,6 +76,41 @@ def student_neighbours(keys: Sequence[str], vectors, *, k: int = DEFAULT_K,
     return rows
 
 
+def _edge_rows(keys, lims, S, I, q0: int, directed: bool, mirror: bool):
+    """(a, b, sim) rows of a join result over query rows q0 ..: ordered by a's
+    position, then b's.  ``mirror``: the result is an upper join (b > a); the
+    directed rows add each pair's (b, a) with the same sim."""
+    counts = np.diff(np.asarray(lims).astype(np.int64))
+    a = np.repeat(np.arange(q0, q0 + counts.size, dtype=np.int64), counts)
+    b = np.asarray(I, dtype=np.int64)
+    s = np.asarray(S, dtype=np.float32)
+    if directed and mirror:
+        a, b, s = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([s, s])
+        order = np.lexsort((b, a))
+        a, b, s = a[order], b[order], s[order]
+    return [(keys[int(x)], keys[int(y)], float(v)) for x, y, v in zip(a, b, s)]
+
+
+def student_edges(keys: Sequence[str], vectors, *, threshold: float = DEFAULT_THRESHOLD,
+                  quantize: bool = True, device: Optional[int] = None,
+                  directed: bool = True) -> List[Tuple[str, str, float]]:
+    """The threshold graph: (a, b, sim) for EVERY pair of students with
+    ``sim >= threshold``, ordered by a's position, then b's — what the
+    refresher's filter (graph_refresher/main.py:350-354) means without its
+    ``LIMIT 15``.
+
+    ``directed=True`` emits both (a, b) and (b, a), the shape of the
+    ``student_similarity`` table; ``directed=False`` each pair once, a before b.
+    Both come from one upper-triangle join (the similarity is symmetric bit for
+    bit), mirrored on the host for the directed form."""
+    keys = list(keys)
+    if len(keys) == 0:
+        return []
+    index = build_student_index(vectors, quantize=quantize, device=device)
+    lims, S, I = index.range_selfjoin(float(threshold), exclude_self=True, upper=True)
+    return _edge_rows(keys, lims, S, I, 0, directed, True)
+
+
 class StudentIndex:
     """Resident student vectors for per-event similarity (the similarity worker,
     src/incremental_workers/similarity/main.py:57-102, runs one student's query
@@ -100,6 +142,23 @@ class StudentIndex:
         S, I = self.index.selfjoin(k, exclude_self=True, min_sim=min_sim)
         return [(self.keys[a], self.keys[int(b)], float(S[a, j]))
                 for a in range(S.shape[0]) for j, b in enumerate(I[a]) if b >= 0]
+
+    def edges(self, threshold: float = DEFAULT_THRESHOLD,
+              directed: bool = True) -> List[Tuple[str, str, float]]:
+        """``student_edges`` over the resident index."""
+        if not self.keys:
+            return []
+        lims, S, I = self.index.range_selfjoin(float(threshold), exclude_self=True, upper=True)
+        return _edge_rows(self.keys, lims, S, I, 0, directed, True)
+
+    def edges_of(self, student: str,
+                 threshold: float = DEFAULT_THRESHOLD) -> List[Tuple[str, str, float]]:
+        """One student's edges, every one at or above the threshold (the
+        similarity worker's event, similarity/main.py:80-94, without its
+        LIMIT), ordered by the neighbour's position."""
+        q = self._row[student]
+        lims, S, I = self.index.range_selfjoin(float(threshold), q0=q, nq=1, exclude_self=True)
+        return _edge_rows(self.keys, lims, S, I, q, True, False)
 
     def upsert(self, student: str, vector) -> None:
         """Insert or replace one student's vector (a removed row compacts the

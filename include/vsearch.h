@@ -382,6 +382,33 @@ int vs_remove_ids(vs_index* idx, const int64_t* ids, int64_t n, int64_t* nremove
 int vs_selfjoin(vs_index* idx, int64_t q0, int64_t nq, int64_t k, int exclude_self,
                 float min_sim, float* D, int64_t* I, int flags, void* stream);
 
+/* Range self-join: the student graph without its LIMIT.  For stored rows q in
+ * [q0, q0+nq): EVERY row r whose cosine similarity with row q is >= min_sim, as
+ * many as there are — the edges `sim >= S.similarity_threshold` that
+ * src/graph_refresher/main.py:339-354 keeps and that its `LIMIT 15` (SQL needs
+ * a k; also src/incremental_workers/similarity/main.py:80-94) cuts at the 15th
+ * neighbour in a dense cluster.  The comparison is not strict (vs_selfjoin's
+ * min_sim, the reference's sim >= threshold).
+ *
+ * A pair is decided by its exact key alone: the fp64 sum of the two stored
+ * rows' products (fp32 x fp32, or bf16 x bf16) rounded once, times the product
+ * of the two rows' inverse norms.  That key is the same bits for (a, b) and
+ * (b, a), so the full join is symmetric, and `upper` != 0 — a query row
+ * reports only the rows after it, r > q — is exactly that half of it, found
+ * with half the multiplications (row tiles below the diagonal are skipped).
+ * exclude_self != 0 leaves row q out of its own hits; `upper` leaves it out by
+ * itself.  Zero-norm rows and a NaN min_sim match nothing.
+ *
+ * The result is a vs_range handle (vs_range_size / vs_range_copy /
+ * vs_range_destroy): D holds the similarities, I the labels row + id_base, each
+ * query's hits in ascending row order.  q0 is a row position; an index with
+ * tombstones is packed first (as vs_selfjoin).  The call synchronises `stream`
+ * (a capturing stream: VS_E_UNSUPPORTED).  nq == 0 or an empty index: lims all
+ * 0.  nq > 65536, or 2^31 or more candidates: VS_E_UNSUPPORTED (callers chunk
+ * the query rows).  flags: none yet (pass 0). */
+int vs_range_selfjoin(vs_index* idx, int64_t q0, int64_t nq, float min_sim, int exclude_self,
+                      int upper, int flags, void* stream, vs_range** out);
+
 /* Merge nparts per-shard top-k lists into one (faiss: the ResultHandler merge;
  * GPU-side half of the RCCL all-gather top-k merge).  Inputs are DEVICE arrays
  * laid out [nparts][nq][k_in] (scores + int64 labels, -1 = empty; raw order for
