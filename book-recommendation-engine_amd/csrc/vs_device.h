@@ -69,6 +69,25 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// A 16-B chunk of a stored row as floats: 4 fp32, or 8 bf16 widened (the
+// streaming kernels gemv_topk and gemv_topk_rows).
+template <typename T>
+__device__ __forceinline__ void widen_chunk(const uint4 v, float (&f)[16 / sizeof(T)]) {
+  if constexpr (sizeof(T) == 4) {
+    f[0] = __uint_as_float(v.x);
+    f[1] = __uint_as_float(v.y);
+    f[2] = __uint_as_float(v.z);
+    f[3] = __uint_as_float(v.w);
+  } else {
+    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __uint_as_float(u[i] << 16);
+      f[2 * i + 1] = __uint_as_float(u[i] & 0xFFFF0000u);
+    }
+  }
+}
+
 // Merges two sorted lists held in LDS (a, b) into registers (best KP of the union).
 template <int KP, typename IdT>
 __device__ __forceinline__ void merge2_sorted(const float* ak, const IdT* ai, const float* bk,

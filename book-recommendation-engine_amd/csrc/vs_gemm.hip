@@ -1,41 +1,14 @@
 // vs_gemm.hip — fused MFMA distance + top-k kernel (large query batches), for
 // fp32 rows (v_mfma_f32_32x32x2_f32) and bf16 rows (v_mfma_f32_32x32x16_bf16).
 // List semantics and key conventions: vs_device.h / vs_internal.h.
-#include "vs_device.h"
+#include "vs_exact_tile.h"
 
 namespace vs {
 
 // ---------------------------------------------------------------------------
-// GEMM path.
-//
-// Workgroup = 256 threads (4 waves), tile = 128 database rows x 128 queries.
-// Wave w owns queries [32w, 32w+32) of the tile against all 128 rows: four
-// 32x32 accumulators (database subtiles s = 0..3).  In v_mfma_f32_32x32x2_f32 the
-// A operand is the database row block (row i = lane&31) and the B operand the
-// query block (column j = lane&31), so after the K loop lane l holds, for query
-// column l&31, the scores of rows (r&3) + 8(r>>2) + 4(l>>5) of each subtile: a
-// lane sees one query only, and can keep that query's top-k in its own
-// registers with no cross-lane traffic.  Each query therefore owns two lists per
-// workgroup (lane halves h = 0, 1); the merge kernel combines them.
-//
-// K loop: BK = 32 floats per stage, double-buffered in LDS and filled with
-// global_load_lds_dwordx4 (no VGPR staging).  An LDS row is 128 B = 8 chunks of
-// 16 B; chunk c of row r is stored at c ^ ((r >> 1) & 7), which makes the
-// ds_read_b128 fragment reads conflict-free (each 16-lane read group lands on 16
-// distinct 16-B slots).  glds writes LDS lane-linearly, so the swizzle is applied
-// to the per-lane GLOBAL source address instead.
-//
-// Fragment k-order: every lane reads one 16-B chunk per operand per step (chunk
-// c = 2*step + h of the 128-B stage row).  fp32: the chunk holds 4 floats and
-// feeds 4 x32x32x2 MFMAs (instruction t uses k = 4h + t of the 8-wide step);
-// bf16: the chunk holds 8 bf16 = exactly the 32x32x16 operand of lane l
-// (k = 8h + j).  A and B use the same mapping, so the product is the plain dot
-// product; the summation order differs from faiss's sgemm, inside the
-// documented fp32 tolerance.  Each stage moves 128 B per row: 32 floats or 64 bf16.
-//
-// Workgroup -> (query tile, split) mapping is XCD-aware: consecutive logical ids
-// (which share a database split and differ in query tile) are packed onto one XCD
-// so the 4 MiB L2 there serves each database tile to all query tiles in flight.
+// GEMM path: the exact tile over contiguous database rows, with a sorted
+// top-k list per lane.  Tile, K loop, fragment k-order and the XCD-aware
+// mapping are described in vs_exact_tile.h.
 //
 // FLOOR (KP = 64 only, every metric): the lists admit only entries that come
 // strictly after the query's floor (fkey[q], fid[q]) in (key, row) order — page
@@ -60,18 +33,11 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk(
   const int h = lane >> 5;
   const int c32 = lane & 31;
 
-  // Bijective XCD remap (blocks b and b+8 are dispatched to the same XCD).
-  const int nblk = gridDim.x;
-  const int b = blockIdx.x;
-  int lb;
-  {
-    const int xcd = b & 7, slot = b >> 3, qq = nblk >> 3, rr = nblk & 7;
-    lb = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int lb = tile_logical_block();
   const int qt = lb % nqt;
   const int sp = lb / nqt;
-  const int t0 = (int)((int64_t)sp * ntiles / nsplit);
-  const int t1 = (int)((int64_t)(sp + 1) * ntiles / nsplit);
+  int t0, t1;
+  tile_split_range(sp, ntiles, nsplit, t0, t1);
 
   // gathered batch (the exact redo of flagged queries): slot s is query row
   // qlist[s]; tiles past the device-side count have nothing to do
@@ -106,8 +72,7 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk(
 #pragma unroll
   for (int par = 0; par < 2; ++par) {
     const int row = par * 8 + srow;  // any group with g & 1 == par has this swizzle
-    const int c = sphys ^ ((row >> 1) & 7);
-    soff[par] = (uint32_t)(w * 32 + srow) * ldb + (uint32_t)c * 16u;
+    soff[par] = (uint32_t)(w * 32 + srow) * ldb + tile_chunk(sphys, row);
   }
   // query source offsets (per lane): contiguous tile rows, or the gathered rows
   // (64-bit: a gathered row of a 65,536-query batch can sit past 4 GiB of
@@ -119,7 +84,7 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk(
       const int slot = qt * kBQ + w * 32 + i * 8 + srow;
       const int src = qlist[min(slot, nf - 1)];
       const int row = (w * 4 + i) * 8 + srow;  // the LDS row decides the swizzle
-      qoff[i] = (uint64_t)src * ldb + (uint32_t)(sphys ^ ((row >> 1) & 7)) * 16u;
+      qoff[i] = (uint64_t)src * ldb + tile_chunk(sphys, row);
     } else {
       qoff[i] = soff[i & 1] + (uint32_t)(i * 8) * ldb;
     }
@@ -206,14 +171,7 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk(
         for (int i = 0; i < 4; ++i) {
           const int row = rb + i;
           const float v = acc[s][j * 4 + i];
-          float key;
-          if constexpr (MODE == MODE_IP) {
-            key = -v;
-          } else if constexpr (MODE == MODE_L2) {
-            key = l2_from_ip(qa, xa[i], v);
-          } else {
-            key = -(v * (qa * xa[i]));
-          }
+          const float key = gemm_key<MODE>(v, qa, xa[i]);
           acc[s][j * 4 + i] = key;
           bool cand = row < ntotal && row != selfrow && lex_less(key, row, tk, ti);
           if constexpr (FLOOR) cand = cand && lex_less(fk, fi, key, row);

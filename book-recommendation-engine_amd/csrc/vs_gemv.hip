@@ -9,24 +9,9 @@ namespace vs {
 // coalesced), the queries sit in LDS, partial sums are reduced across the wave,
 // and lane q keeps query q's list.  MODE_L2D computes sum (x-q)^2 directly, as
 // faiss does for nq < 20 (fvec_L2sqr); MODE_IP the plain dot product.  Rows are
-// fp32 or bf16 (widened in registers); a 16-B chunk is 4 or 8 elements.
-template <typename T>
-__device__ __forceinline__ void widen_chunk(const uint4 v, float (&f)[16 / sizeof(T)]) {
-  if constexpr (sizeof(T) == 4) {
-    f[0] = __uint_as_float(v.x);
-    f[1] = __uint_as_float(v.y);
-    f[2] = __uint_as_float(v.z);
-    f[3] = __uint_as_float(v.w);
-  } else {
-    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(u[i] << 16);
-      f[2 * i + 1] = __uint_as_float(u[i] & 0xFFFF0000u);
-    }
-  }
-}
-
+// fp32 or bf16 (widened in registers, vs_device.h widen_chunk); a 16-B chunk is
+// 4 or 8 elements.
+//
 // FLOOR: query q's list admits only rows strictly after (fkey[q], fid[q]) in
 // (key, row) order (page p + 1 of the paged engine, vs_engines.hip run_paged; a
 // query with nothing left to page gets the floor (+inf, INT_MAX) and an empty

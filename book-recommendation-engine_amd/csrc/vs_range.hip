@@ -10,16 +10,17 @@
 #include <algorithm>
 #include <cmath>
 
+#include "vs_exact_tile.h"
 #include "vs_x1_device.h"
 
 namespace vs {
 
 // ---------------------------------------------------------------------------
-// The candidate passes.  The main loop is gemm_topk's (vs_gemm.hip: the same
-// 128 x 128 tile, glds staging, swizzle, MFMAs, XCD remap and (query tile,
-// split) mapping), restated here so that gemm_topk's code stays as it is; the
-// epilogue tests a row's key against its query's threshold instead of keeping
-// lists.  After the K loop a lane holds, for ONE query, the keys of rows
+// The candidate passes.  gemm_range runs the exact tile described in
+// vs_exact_tile.h (gemm_topk's 128 x 128 tile, glds staging, swizzle and MFMAs;
+// the mapping and the keys are that header's) and adds the UPPER tile range and
+// an epilogue that tests a row's key against its query's threshold instead of
+// keeping lists.  After the K loop a lane holds, for ONE query, the keys of rows
 // 32 s + 8 j + 4 h + i of subtile s (h = its lane half, register (j, i)), so a
 // query's hits of a subtile are two 16-bit masks, one per lane half.
 //
@@ -59,25 +60,17 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
   const int h = lane >> 5;
   const int c32 = lane & 31;
 
-  // Bijective XCD remap (blocks b and b+8 are dispatched to the same XCD).
-  const int nblk = gridDim.x;
-  const int b = blockIdx.x;
-  int lb;
-  {
-    const int xcd = b & 7, slot = b >> 3, qq = nblk >> 3, rr = nblk & 7;
-    lb = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int lb = tile_logical_block();
   const int qt = lb % nqt;
   const int sp = lb / nqt;
   int t0, t1;
   if constexpr (UPPER) {
     const int tlo = min((qrow0 + qt * kBQ) / kBN, ntiles);
-    const int nt = ntiles - tlo;
-    t0 = tlo + (int)((int64_t)sp * nt / nsplit);
-    t1 = tlo + (int)((int64_t)(sp + 1) * nt / nsplit);
+    tile_split_range(sp, ntiles - tlo, nsplit, t0, t1);
+    t0 += tlo;
+    t1 += tlo;
   } else {
-    t0 = (int)((int64_t)sp * ntiles / nsplit);
-    t1 = (int)((int64_t)(sp + 1) * ntiles / nsplit);
+    tile_split_range(sp, ntiles, nsplit, t0, t1);
   }
 
   const int qloc = 32 * w + c32;
@@ -105,8 +98,7 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
 #pragma unroll
   for (int par = 0; par < 2; ++par) {
     const int row = par * 8 + srow;  // any group with g & 1 == par has this swizzle
-    const int c = sphys ^ ((row >> 1) & 7);
-    soff[par] = (uint32_t)(w * 32 + srow) * ldb + (uint32_t)c * 16u;
+    soff[par] = (uint32_t)(w * 32 + srow) * ldb + tile_chunk(sphys, row);
   }
   // fragment-read geometry: (row >> 1) & 7 is the same for every subtile.
   const int fsw = (c32 >> 1) & 7;
@@ -168,8 +160,8 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
       __syncthreads();
     }
 
-    // Epilogue, one 32-row subtile at a time: scores -> keys (gemm_topk's
-    // expressions) -> the 16-bit mask of the rows at or below the threshold.
+    // Epilogue, one 32-row subtile at a time: scores -> keys (gemm_key) -> the
+    // 16-bit mask of the rows at or below the threshold.
     const int r0 = t * kBN;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -183,10 +175,7 @@ __global__ __launch_bounds__(256, 2) void gemm_range(
         for (int i = 0; i < 4; ++i) {
           const int row = rb + i;
           const float v = acc[s][j * 4 + i];
-          float key;
-          if constexpr (MODE == MODE_IP) key = -v;
-          else if constexpr (MODE == MODE_L2) key = l2_from_ip(qa, xa[i], v);
-          else key = -(v * (qa * xa[i]));
+          const float key = gemm_key<MODE>(v, qa, xa[i]);
           const bool hit = row < ntotal && key <= th;  // a NaN key or threshold: no
           m |= (uint32_t)hit << (j * 4 + i);
         }

@@ -22,7 +22,7 @@
 // kernel uses the norm expansion |q|^2 + |x|^2 - 2 q.x clamped at 0, as
 // gemm_topk does (the two agree within the fp32 tolerance the tests document
 // for gemm_topk).
-#include "vs_device.h"
+#include "vs_exact_tile.h"
 
 namespace vs {
 
@@ -215,11 +215,12 @@ hipError_t launch_sel_drop(int mode, const float* Din, const int64_t* Iin, int n
 }
 
 // ---------------------------------------------------------------------------
-// gemm_topk_rows: a database tile is 128 consecutive list entries.  Each lane's
-// X source offset is its list row times the row stride (64-bit, a row can sit
-// past 4 GiB) plus the swizzled chunk, the way gemm_topk's qoff[] gathers
-// queries; the epilogue reads the tile's rows from the list again, gathers
-// xaux[row] and masks the entries past `count` (the list's padding).
+// gemm_topk_rows: the exact tile of vs_exact_tile.h (its mapping and keys)
+// with a database tile of 128 consecutive list entries.  What it adds: each
+// lane's X source offset is its list row times the row stride (64-bit, a row
+// can sit past 4 GiB) plus the swizzled chunk, reloaded per tile; the epilogue
+// reads the tile's rows from the list again, gathers xaux[row] and masks the
+// entries past `count` (the list's padding).
 template <int KP, int MODE, typename T>
 __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk_rows(
     const T* __restrict__ X, const float* __restrict__ xaux, const T* __restrict__ Q,
@@ -236,17 +237,11 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk_rows(
   const int h = lane >> 5;
   const int c32 = lane & 31;
 
-  const int nblk = gridDim.x;
-  const int b = blockIdx.x;
-  int lb;
-  {
-    const int xcd = b & 7, slot = b >> 3, qq = nblk >> 3, rr = nblk & 7;
-    lb = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int lb = tile_logical_block();
   const int qt = lb % nqt;
   const int sp = lb / nqt;
-  const int t0 = (int)((int64_t)sp * ntiles / nsplit);
-  const int t1 = (int)((int64_t)(sp + 1) * ntiles / nsplit);
+  int t0, t1;
+  tile_split_range(sp, ntiles, nsplit, t0, t1);
 
   const int qloc = 32 * w + c32;
   const int gq = qt * kBQ + qloc;
@@ -266,6 +261,8 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk_rows(
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int row = (w * 4 + i) * 8 + srow;  // the LDS row decides the swizzle
+    // tile_chunk(sphys, row), written out: through the helper this kernel's
+    // instruction streams change (profiles/exact_tile/code_objects.txt)
     xsw[i] = (uint32_t)(sphys ^ ((row >> 1) & 7)) * 16u;
     qoff[i] = (uint32_t)(w * 32 + i * 8 + srow) * ldb + xsw[i];
   }
@@ -345,12 +342,9 @@ __global__ __launch_bounds__(256, (KP >= 64 ? 1 : 2)) void gemm_topk_rows(
         for (int i = 0; i < 4; ++i) {
           const int row = rows[i];
           const float v = acc[s][j * 4 + i];
-          float key;
-          if constexpr (MODE == MODE_IP) {
-            key = -v;
-          } else {
-            key = l2_from_ip(qa, xaux[row], v);
-          }
+          float xa = 0.0f;
+          if constexpr (MODE == MODE_L2) xa = xaux[row];
+          const float key = gemm_key<MODE>(v, qa, xa);
           acc[s][j * 4 + i] = key;
           const bool cand = eb + i < count && lex_less(key, row, tk, ti);
           m |= (uint32_t)cand << (j * 4 + i);
@@ -438,23 +432,6 @@ hipError_t launch_gemm_topk_rows(int KP, int mode, const void* X, const float* x
 
 // ---------------------------------------------------------------------------
 // gemv_topk_rows: gemv_topk over list positions; position p is row list[p].
-template <typename T>
-__device__ __forceinline__ void widen_chunk_rows(const uint4 v, float (&f)[16 / sizeof(T)]) {
-  if constexpr (sizeof(T) == 4) {
-    f[0] = __uint_as_float(v.x);
-    f[1] = __uint_as_float(v.y);
-    f[2] = __uint_as_float(v.z);
-    f[3] = __uint_as_float(v.w);
-  } else {
-    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(u[i] << 16);
-      f[2 * i + 1] = __uint_as_float(u[i] & 0xFFFF0000u);
-    }
-  }
-}
-
 template <int NQ, int KP, int MODE, typename T>
 __global__ __launch_bounds__(256) void gemv_topk_rows(const T* __restrict__ X,
                                                       const float* __restrict__ Q, int64_t ld,
@@ -501,7 +478,7 @@ __global__ __launch_bounds__(256) void gemv_topk_rows(const T* __restrict__ X,
       }
       float xf[4][EPC];
 #pragma unroll
-      for (int a = 0; a < 4; ++a) widen_chunk_rows<T>(xv[a], xf[a]);
+      for (int a = 0; a < 4; ++a) widen_chunk<T>(xv[a], xf[a]);
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         float qf[EPC];

@@ -100,6 +100,38 @@ def test_bf16_recall_vs_fp32(vf, metric):
     assert recall >= 0.9, recall
 
 
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_bf16_single_stage_k_loop(vf, metric):
+    """d = 64 on a bf16 index is one 128-byte stage of the exact MFMA tile's K
+    loop (no prefetch of a next stage), at 130 queries (two query tiles, the
+    second padded) and 300 rows (three row tiles, the last with 44 live rows):
+    gemm_topk through the fp32 engine, gemm_topk_rows through a selector of 40
+    rows (more than 256 rows left out, so the gathered kernels serve it)."""
+    from vsearch import _lib
+
+    xb, xq = _rand(300, 64, 11), _rand(130, 64, 12)
+    index = vf.IndexFlat(64, metric, dtype="bf16")
+    index.add(xb)
+    index.set_engine("fp32")
+    rb, rq = flat.round_bf16(xb), flat.round_bf16(xq)
+    D, I = index.search(xq, 10)
+    assert _lib.timer_kernel() == "gemm_topk"
+    Dr, Ir = flat.knn_exact(rb, rq, 10, metric)
+    bad = flat.mismatches(D, I, Dr, Ir, metric, rb, rq)
+    assert not bad, bad[:5]
+
+    mask = np.zeros(300, dtype=bool)
+    mask[np.random.default_rng(13).choice(300, 40, replace=False)] = True
+    sel = index.selector(vf.IDSelectorBitmap(300, np.packbits(mask, bitorder="little")))
+    D, I = index.search(xq, 10, params=vf.SearchParameters(sel=sel))
+    assert _lib.timer_kernel() == "gemm_topk_rows"
+    assert mask[I].all()
+    Dr, Ir = flat.select_topk(flat.exact_scores(rb, rq, metric), 10, metric,
+                              valid=mask[None, :].repeat(130, 0), rule="faiss")
+    bad = flat.mismatches(D, I, Dr, Ir, metric, rb, rq)
+    assert not bad, bad[:5]
+
+
 def test_bf16_selfjoin(vf):
     x = _rand(700, 48, 8)
     index = vf.IndexFlatIP(48, dtype="bf16")
