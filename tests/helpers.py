@@ -160,3 +160,136 @@ def proven_candidates(index, xs, metric, N, K, m=64, chunk=1_000_000):
         xn2 = np.einsum("ij,ij->i", xb.astype(np.float64), xb.astype(np.float64))
         res.append((ids, exact, xn2, qn * qn))
     return res
+
+
+# Row families that stress the staged engine's data-dependent bounds (DESIGN.md
+# §4.3): per-row int8 scales, residual norms, the index maxima, the L2
+# augmentation and the absolute constants.  Every value is finite.
+ROW_FAMILIES = ("ladder", "spike", "offset", "sparse", "zeros", "late",
+                "pow2:-40", "pow2:0", "pow2:40")
+# The shapes tests/test_gpu_row_families.py searches and
+# tests/test_row_families_host.py admits: (n, d, nq, k, seed).  d = 100 pads to
+# ld = 128, nq = 100 is one full and one ragged query tile; FAMILY_WIDE is the
+# ladder at ld = 1024, where l2aug_params' cap lets m reach 128.
+FAMILY_SHAPE = (6000, 100, 100, 10, 7)
+FAMILY_WIDE = (3000, 1024, 100, 10, 7)
+FAMILY_JOIN_ROWS = 300  # stored rows the cosine self-joins query
+FAMILY_WIDEST_K = {0: 28, 1: 56}  # metric -> the widest list the staged engine takes
+ZERO_QUERIES = (5, 70)  # queries the "zeros" searches also set to zero
+
+
+def zero_rows(n):
+    """The rows row_family("zeros", n, ...) sets to zero."""
+    return (0, n // 2, n - 1)
+
+
+def family_case(name, n, d, nq, seed):
+    """row_family as the searches use it: the "zeros" batch also has its
+    ZERO_QUERIES set to zero."""
+    xb, xq = row_family(name, n, d, nq, seed)
+    if name == "zeros":
+        xq[[q for q in ZERO_QUERIES if q < nq]] = 0.0
+    return xb, xq
+
+
+def family_skip(name, n):
+    """(rows, queries) free_share leaves out for a family: the zero rows and
+    zero queries of "zeros" (checked on their own), nothing otherwise."""
+    return (zero_rows(n), ZERO_QUERIES) if name == "zeros" else None
+
+
+def row_family(name, n, d, nq, seed):
+    """Deterministic (xb (n, d), xq (nq, d)) float32 rows of one family, drawn
+    with g(m) = rng.standard_normal((m, d)) on one default_rng(seed):
+      ladder   g * 10**U(-2, 2) per row and per query: norms log-uniform over
+               four decades;
+      spike    one coordinate per row and per query (random position) times 64;
+      offset   mu + g, mu = 8 sign(g(1)) shared by rows and queries;
+      sparse   rows of four non-zero standard-normal entries at random
+               positions, dense queries;
+      zeros    g with rows 0, n // 2, n - 1 set to zero;
+      late     g with the last n // 10 rows times 100;
+      pow2:e   ldexp(g, e) for rows and queries."""
+    rng = np.random.default_rng(seed)
+
+    def g(m):
+        return rng.standard_normal((m, d))
+
+    if name == "ladder":
+        xb = g(n) * 10.0 ** rng.uniform(-2, 2, (n, 1))
+        xq = g(nq) * 10.0 ** rng.uniform(-2, 2, (nq, 1))
+    elif name == "spike":
+        xb, xq = g(n), g(nq)
+        xb[np.arange(n), rng.integers(0, d, n)] *= 64.0
+        xq[np.arange(nq), rng.integers(0, d, nq)] *= 64.0
+    elif name == "offset":
+        mu = 8.0 * np.sign(g(1))
+        xb, xq = mu + g(n), mu + g(nq)
+    elif name == "sparse":
+        xb = np.zeros((n, d))
+        for i in range(n):
+            xb[i, rng.choice(d, 4, replace=False)] = rng.standard_normal(4)
+        xq = g(nq)
+    elif name == "zeros":
+        xb, xq = g(n), g(nq)
+        xb[[0, n // 2, n - 1]] = 0.0
+    elif name == "late":
+        xb, xq = g(n), g(nq)
+        xb[n - n // 10:] *= 100.0
+    elif name.startswith("pow2:"):
+        e = int(name[5:])
+        xb, xq = np.ldexp(g(n), e), np.ldexp(g(nq), e)
+    else:
+        raise ValueError(name)
+    return xb.astype(np.float32), xq.astype(np.float32)
+
+
+def _share(sorted_scores, windows, k):
+    """Share of (query, rank j < k) positions whose j-th and (j+1)-th sorted
+    scores lie within the sum of their two windows."""
+    gap = np.abs(sorted_scores[:, 1:k + 1] - sorted_scores[:, :k])
+    free = gap <= windows[:, 1:k + 1] + windows[:, :k]
+    return float(free.mean()) if free.size else 0.0
+
+
+def free_share(xb, xq, metric, k, skip=None):
+    """From the oracle alone: the share of (query, rank j < k) positions where
+    the oracle's j-th and (j+1)-th scores lie within the sum of their two
+    strict windows (flat.key_window), i.e. where flat.mismatches(strict=True)
+    would accept either label.  skip = (rows, queries) left out of the count."""
+    xb = np.asarray(xb, dtype=np.float32)
+    xq = np.asarray(xq, dtype=np.float32)
+    rows, queries = skip if skip is not None else ((), ())
+    keep_r = np.setdiff1d(np.arange(xb.shape[0]), np.asarray(rows, dtype=np.int64))
+    keep_q = np.setdiff1d(np.arange(xq.shape[0]), np.asarray(queries, dtype=np.int64))
+    xb, xq = xb[keep_r], xq[keep_q]
+    s = flat.exact_scores(xb, xq, metric)
+    xn2 = np.einsum("ij,ij->i", xb.astype(np.float64), xb.astype(np.float64))
+    qn2 = np.einsum("ij,ij->i", xq.astype(np.float64), xq.astype(np.float64))
+    w = flat.key_window(metric, s, qn2[:, None], xn2[None, :], xb.shape[1])
+    key = s if metric == flat.METRIC_L2 else -s
+    order = np.argsort(key, axis=1, kind="stable")[:, :k + 1]
+    return _share(np.take_along_axis(s, order, axis=1), np.take_along_axis(w, order, axis=1), k)
+
+
+def free_share_cosine(x, k, q_rows, skip=None):
+    """free_share for the cosine self-join of stored rows q_rows of x (self
+    excluded, zero-norm rows never match): windows from
+    flat.key_window(..., cosine=True).  skip = rows left out, as rows and as
+    queries."""
+    x64 = np.asarray(x, dtype=np.float64)
+    q_rows = np.asarray(q_rows, dtype=np.int64)
+    if skip is not None:
+        q_rows = np.setdiff1d(q_rows, np.asarray(skip, dtype=np.int64))
+    nrm = np.sqrt(np.einsum("ij,ij->i", x64, x64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sims = (x64[q_rows] @ x64.T) / (nrm[q_rows, None] * nrm[None, :])
+    sims[np.arange(q_rows.size), q_rows] = -np.inf
+    if skip is not None:
+        sims[:, np.asarray(skip, dtype=np.int64)] = -np.inf
+    sims[~np.isfinite(sims)] = -np.inf
+    order = np.argsort(-sims, axis=1, kind="stable")[:, :k + 1]
+    s = np.take_along_axis(sims, order, axis=1)
+    assert np.isfinite(s).all()
+    w = flat.key_window(0, s, 0, 0, x64.shape[1], cosine=True)
+    return _share(s, w, k)
