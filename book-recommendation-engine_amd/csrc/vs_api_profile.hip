@@ -299,6 +299,20 @@ int check_excl_lists(const char* what, const int64_t* excl_offs, const int64_t* 
   return VS_OK;
 }
 
+int run_excluded_chunk(vs_index* idx, const SearchArgs& a, const int64_t* hoffs,
+                       const int64_t* doffs, const int64_t* drows, hipStream_t st) {
+  return run_excluded(idx, a, hoffs, doffs, drows, st);
+}
+
+void excl_rows_build(const vs_index* idx, int64_t n, const int64_t* excl_offs,
+                     const int64_t* excl_labels, std::vector<int64_t>* offs,
+                     std::vector<int64_t>* rows) {
+  ExclSets es;
+  build_excl_sets(idx, n, excl_offs, excl_labels, nullptr, nullptr, &es);
+  offs->swap(es.offs);
+  rows->swap(es.rows);
+}
+
 int search_excl_held(vs_index* idx, const float* x, int64_t n, int64_t k, const int64_t* excl_offs,
                      const int64_t* excl_labels, float* D, int64_t* I, int flags, hipStream_t st) {
   ExclSets es;

@@ -118,6 +118,19 @@ struct vs_selector {
   int* list = nullptr;        // [count rounded up to kBN] ascending rows, padded
 };
 
+// A grouping of one index (vs_grouping_create): the group of every row in
+// place (tombstoned rows hold -1; no search returns them), valid while the
+// index's generation is the one it was built at.
+struct vs_grouping {
+  vs_index* idx = nullptr;
+  int device = 0;
+  uint64_t gen = 0;
+  int64_t n = 0;       // labels given = the live rows at creation
+  int64_t nrows = 0;   // rows in place the device copy covers
+  int64_t groups = 0;  // distinct groups, every -1 row counted as one
+  int32_t* dgroup = nullptr;  // [nrows]
+};
+
 // Route (b) of vs_search_sel serves selections that leave at most this many
 // live rows out (a fixed condition of the route, not a tuned threshold).
 constexpr int64_t kSelMaxExcluded = 256;
@@ -536,6 +549,35 @@ int check_excl_lists(const char* what, const int64_t* excl_offs, const int64_t* 
 // arguments checked.
 int search_excl_held(vs_index* idx, const float* x, int64_t n, int64_t k, const int64_t* excl_offs,
                      const int64_t* excl_labels, float* D, int64_t* I, int flags, hipStream_t st);
+
+// One chunk of a search with exclusion sets (run_excluded) for
+// vs_search_distinct: hoffs / doffs = the chunk's nq + 1 CSR offsets (host /
+// device) into drows, the excluded rows in place, every segment ascending and
+// distinct.
+int run_excluded_chunk(vs_index* idx, const SearchArgs& a, const int64_t* hoffs,
+                       const int64_t* doffs, const int64_t* drows, hipStream_t st);
+// The exclusion sets of n queries as rows in place (labels that are not live
+// labels, -1 and duplicates dropped): offs (n + 1, from 0) and rows.  The
+// caller holds the reader lock.
+void excl_rows_build(const vs_index* idx, int64_t n, const int64_t* excl_offs,
+                     const int64_t* excl_labels, std::vector<int64_t>* offs,
+                     std::vector<int64_t>* rows);
+
+// ---- distinct searches (vs_api_distinct.hip) ---------------------------------
+// The entries a distinct search's answer is a function of: faiss's
+// inner-product rule reads 2k - 1, every other order k.
+inline int64_t distinct_need(int64_t k, int metric, int raw) {
+  return metric == VS_METRIC_INNER_PRODUCT && !raw ? 2 * k - 1 : k;
+}
+// The window (raw entries per query) of round `round` of a distinct search
+// over `live` rows: need + max(16, need / 2), four times longer every round,
+// clipped to the live rows.  A cost knob only: any non-decreasing schedule
+// that ends at the live rows is exact (DESIGN.md "Distinct searches").
+inline int64_t distinct_window(int64_t need, int round, int64_t live) {
+  int64_t w = need + std::max<int64_t>(16, need / 2);
+  for (int r = 0; r < round && w < live; ++r) w *= 4;
+  return std::min(w, live);
+}
 
 }  // namespace host
 }  // namespace vs

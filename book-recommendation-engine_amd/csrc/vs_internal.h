@@ -634,4 +634,24 @@ hipError_t launch_mmr_pick(const void* X, int esize, int64_t ld, const int64_t* 
                            int* pos, const float* Dc, const int64_t* Ic, float pad, float* Dout,
                            int64_t* Iout, hipStream_t st);
 
+// Distinct searches (vs_distinct.hip; vs_api_distinct.hip vs_search_distinct).
+// The most groups one collapse keeps: its LDS table holds 2 * 2047 groups
+// (inner product under faiss's rule at k = 1024 reads 2k - 1 = 2047).
+constexpr int kDistinctMaxK = 1024;
+// Slot s of Din / Iin ([ns][w] raw entries: ascending (key, label), labels =
+// row + id_base, -1 after the end) -> row s of Dout / Iout ([ns][kout]): the
+// first entry of every group in window order (group[row], ngroup rows; -1: the
+// row is its own group), at most `need` of them, padded with the empty result
+// of `mode`; kept[s] (may be null) = how many; unsettled[qmap ? qmap[s] : s] =
+// 1 when the window was too short (fewer than `need` kept, no -1 entry seen,
+// and not w_is_all), else 0.  need <= 2047.
+hipError_t launch_distinct_collapse(int mode, const float* Din, const int64_t* Iin, int ns, int w,
+                                    const int32_t* group, int64_t ngroup, int64_t id_base,
+                                    int need, bool w_is_all, const int* qmap, float* Dout,
+                                    int64_t* Iout, int kout, int* kept, int* unsettled,
+                                    hipStream_t st);
+// Row qmap[s] of Dout / Iout = row s of Din / Iin ([ns][k]).
+hipError_t launch_distinct_scatter(const float* Din, const int64_t* Iin, int ns, int k,
+                                   const int* qmap, float* Dout, int64_t* Iout, hipStream_t st);
+
 }  // namespace vs

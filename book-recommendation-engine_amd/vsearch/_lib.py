@@ -68,6 +68,13 @@ SIGNATURES = {
     "vs_mean_rows": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_int, _vp]),
     "vs_search_profiles": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
                                     _vp, _c_int, _vp]),
+    "vs_grouping_create": (_c_int, [_vp, _vp, _c_i64, _vp, ctypes.POINTER(_vp)]),
+    "vs_grouping_groups": (_c_int, [_vp, _i64p]),
+    "vs_grouping_destroy": (_c_int, [_vp]),
+    "vs_search_distinct": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_int,
+                                    _vp]),
+    "vs_distinct_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _vp, _c_int]),
+    "vs_distinct_stats": (_c_int, [_i64p, _i64p, _i64p, _c_int]),
     "vs_mmr_select": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_double, _vp, _c_int,
                                _vp]),
     "vs_search_mmr": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, ctypes.c_double, _vp, _vp, _vp,

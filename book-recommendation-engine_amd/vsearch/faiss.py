@@ -332,6 +332,84 @@ class Selector:
         self.close()
 
 
+def group_ids(keys) -> np.ndarray:
+    """Group keys factorised to the int32 ids of a grouping: an integer array
+    passes through (values >= -1; -1 is "this row is its own group"); any other
+    sequence of hashables gets dense ids 0, 1, ... in order of first
+    appearance, equal keys equal ids, and ``None`` gives -1."""
+    if isinstance(keys, np.ndarray) and keys.dtype.kind in "iu":
+        ids = keys.ravel()
+        if ids.size and (ids.min() < -1 or ids.max() > np.iinfo(np.int32).max):
+            raise ValueError("group_ids: integer keys must lie in [-1, 2^31)")
+        return np.ascontiguousarray(ids, dtype=np.int32)
+    keys = list(keys)
+    if keys and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in keys):
+        return group_ids(np.asarray(keys, dtype=np.int64))
+    seen: dict = {}
+    out = np.empty(len(keys), dtype=np.int32)
+    for i, v in enumerate(keys):
+        out[i] = -1 if v is None else seen.setdefault(v, len(seen))
+    return out
+
+
+class Grouping:
+    """Device handle of a grouping of one index (``IndexFlat.grouping``): one
+    group id per label.  Reusable across ``search_distinct`` calls until the
+    index changes (add, remove_ids, reset), after which searching with it
+    raises RuntimeError ("stale grouping").  ``.groups`` is the number of
+    distinct groups, every row that is its own group counted as one."""
+
+    def __init__(self, index: "IndexFlat", ids: np.ndarray):
+        self._lib = index._lib
+        self._h = ctypes.c_void_p()
+        self.index = index
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        _lib.check(self._lib.vs_grouping_create(index._h, _ptr(ids), int(ids.size), None,
+                                                ctypes.byref(self._h)), "vs_grouping_create")
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.vs_grouping_groups(self._h, ctypes.byref(n)), "vs_grouping_groups")
+        self.groups = int(n.value)
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h is None or not h.value:
+            return
+        try:
+            self._lib.vs_grouping_destroy(h)
+        except Exception:  # interpreter shutdown: the library may be gone
+            pass
+        h.value = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def distinct_plan(k: int, metric: int, raw: bool, live: int):
+    """The windows (raw entries per query) of a distinct search for k over
+    ``live`` rows, round by round (vs_distinct_plan; touches no device)."""
+    lib = _lib.load()
+    out = np.zeros(64, dtype=np.int64)
+    n = lib.vs_distinct_plan(int(k), int(metric), 1 if raw else 0, int(live), out.ctypes.data,
+                             out.size)
+    _lib.check(min(n, 0), "vs_distinct_plan")
+    return [int(v) for v in out[:n]]
+
+
+def distinct_stats(reset: bool = False):
+    """(queries searched, rounds run, queries searched again) of the distinct
+    searches of this process since the last reset."""
+    a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().vs_distinct_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                             1 if reset else 0), "vs_distinct_stats")
+    return a.value, b.value, c.value
+
+
 class Index:
     """Common base (faiss.Index)."""
 
@@ -556,6 +634,55 @@ class IndexFlat(Index):
                                        I.ctypes.data, _lib.RAW_ORDER if raw else 0, None),
                    "vs_search")
         return D, I
+
+    def grouping(self, keys) -> Grouping:
+        """The device handle of a grouping: ``keys`` holds one key per label
+        (``ntotal`` of them): ints (-1: its own group) or any hashables
+        (``None``: its own group), factorised by ``group_ids``."""
+        if isinstance(keys, Grouping):
+            return keys
+        return Grouping(self, group_ids(keys))
+
+    def search_distinct(self, x, k, grouping, *, exclude=None, raw: bool = False):
+        """The k nearest groups, one best row per group: what ``search`` would
+        return on an index that held only each group's best row (its lowest
+        label among equally good ones).  ``grouping`` is a ``Grouping`` from
+        ``index.grouping``, or the keys of one (built and freed in this call);
+        ``exclude`` and ``raw`` as in ``search``.  Fewer than k groups among
+        the allowed rows pad with label -1.  Exact for any grouping; k <= 1024."""
+        x = _as_f32_rows(x)
+        n, d = x.shape
+        assert d == self._d
+        k = int(k)
+        assert k > 0
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        owned = not isinstance(grouping, Grouping)
+        grp = self.grouping(grouping)
+        if grp.index is not self:
+            raise ValueError("the Grouping belongs to another index")
+        try:
+            offs, labels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+            _lib.check(self._lib.vs_search_distinct(
+                self._h, grp._h, _ptr(x), n, k,
+                offs.ctypes.data if offs is not None else None,
+                _ptr(labels) if labels is not None else None, _ptr(D), _ptr(I),
+                _lib.RAW_ORDER if raw else 0, None), "vs_search_distinct")
+        finally:
+            if owned:
+                grp.close()
+        return D, I
+
+    def search_distinct_device(self, xq_ptr: int, n: int, k: int, grouping: Grouping, D_ptr: int,
+                               I_ptr: int, stream: int = 0, raw: bool = False) -> None:
+        """``search_distinct`` with every buffer on this index's device, on
+        `stream` (the call waits for the stream after every round but the
+        last; a capturing stream is refused)."""
+        flags = _lib.IN_DEVICE | _lib.OUT_DEVICE | (_lib.RAW_ORDER if raw else 0)
+        _lib.check(self._lib.vs_search_distinct(
+            self._h, grouping._h, ctypes.c_void_p(xq_ptr), int(n), int(k), None, None,
+            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags, ctypes.c_void_p(stream)),
+            "vs_search_distinct")
 
     def mean_rows(self, profiles) -> np.ndarray:
         """The weighted means of stored rows, computed on the device: profile

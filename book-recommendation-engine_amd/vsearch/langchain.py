@@ -212,6 +212,8 @@ class FAISS:
         self._keymap: Dict[Any, List[str]] = {}
         # exact_filter selectors by the filter's JSON; dropped by every add / delete / merge
         self._sel_cache: Dict[str, Any] = {}
+        # distinct= groupings by metadata field; dropped whenever _sel_cache is
+        self._grp_cache: Dict[str, Any] = {}
         # (field, metadata[field] -> labels), built once per store generation
         # (the labels move with every delete): dropped with _sel_cache
         self._keylabels: Optional[Tuple[str, Dict[Any, List[int]]]] = None
@@ -257,6 +259,7 @@ class FAISS:
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
         self._sel_cache.clear()
+        self._grp_cache.clear()
         self._keylabels = None
         self.index.add(vector)
         self.docstore.add({id_: doc for id_, doc in zip(ids, documents)})
@@ -357,6 +360,7 @@ class FAISS:
         reversed_index = {id_: idx for idx, id_ in self.index_to_docstore_id.items()}
         index_to_delete = {reversed_index[id_] for id_ in ids}
         self._sel_cache.clear()
+        self._grp_cache.clear()
         self._keylabels = None
         self.index.remove_ids(np.fromiter(index_to_delete, dtype=np.int64))
         if self._keymap_field is not None:
@@ -383,6 +387,7 @@ class FAISS:
             raise ValueError("Cannot merge with this type of docstore")
         index_offset = len(self.index_to_docstore_id)
         self._sel_cache.clear()
+        self._grp_cache.clear()
         self._keylabels = None
         if target.index.ntotal:
             self.index.add(target.index.reconstruct_n(0, target.index.ntotal))
@@ -475,6 +480,20 @@ class FAISS:
             self._sel_cache[key] = sel
         return sel
 
+    def _distinct_grouping(self, field: str):
+        """What ``index.search_distinct`` takes for ``distinct=field``: one key
+        per label, metadata[field] of its document (a document without the
+        field is its own group), as the index's device handle.  Built once per
+        field and kept until the store changes."""
+        grp = self._grp_cache.get(field)
+        if grp is None:
+            keys = []
+            for i in range(len(self.index_to_docstore_id)):
+                doc = self.docstore.search(self.index_to_docstore_id[i])
+                keys.append(doc.metadata.get(field) if isinstance(doc, Document) else None)
+            grp = self._grp_cache[field] = self.index.grouping(keys)
+        return grp
+
     # -- reads ------------------------------------------------------------------------------
     def similarity_search_with_score_by_vector(self, embedding: List[float], k: int = 4,
                                                filter: Optional[Any] = None, fetch_k: int = 20,
@@ -486,16 +505,33 @@ class FAISS:
 
         ``exclude_ids=[...]`` (docstore ids; unknown ones are ignored): those
         documents are left out of the search itself, so k others come back
-        (library-specific; not together with ``exact_filter``)."""
+        (library-specific; not together with ``exact_filter``).
+
+        ``distinct="<metadata field>"``: at most one document per value of that
+        field, each value's nearest document (``index.search_distinct``): the
+        k nearest books of a store that holds several rows per book, where a
+        plain search returns a re-ingested book twice.  Documents without the
+        field count one by one.  With a host `filter` the distinct search
+        fetches `fetch_k` values and the filter runs after it; not together
+        with ``exact_filter`` (library-specific)."""
         vector = np.array([embedding], dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
         exclude_ids = kwargs.get("exclude_ids")
+        distinct = kwargs.get("distinct")
+        if distinct is not None and exact_filter:
+            raise ValueError("distinct and exact_filter cannot be combined")
+        drop = None
         if exclude_ids is not None:
             if exact_filter and filter is not None:
                 raise ValueError("exclude_ids and exact_filter cannot be combined")
             wanted = set(exclude_ids)
             drop = [i for i, id_ in self.index_to_docstore_id.items() if id_ in wanted]
+        if distinct is not None:
+            scores, indices = self.index.search_distinct(
+                vector, k if filter is None else fetch_k, self._distinct_grouping(distinct),
+                exclude=None if drop is None else [drop])
+        elif drop is not None:
             scores, indices = self.index.search(vector, k if filter is None else fetch_k,
                                                 exclude=[drop])
         elif exact_filter and filter is not None:
@@ -581,13 +617,19 @@ class FAISS:
         return self.similarity_search_within_score_by_vector(self._embed_query(query),
                                                              score_threshold, filter=filter)
 
-    def similarity_search_batch_by_vector(self, embeddings, k: int = 4):
+    def similarity_search_batch_by_vector(self, embeddings, k: int = 4,
+                                          distinct: Optional[str] = None):
         """Batched variant (one engine call for many queries): list of
-        [(Document, score)] per query, label -1 skipped."""
+        [(Document, score)] per query, label -1 skipped.  ``distinct`` as in
+        ``similarity_search_with_score_by_vector``."""
         vec = np.array(embeddings, dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vec)
-        scores, indices = self.index.search(vec, k)
+        if distinct is not None:
+            scores, indices = self.index.search_distinct(vec, k,
+                                                         self._distinct_grouping(distinct))
+        else:
+            scores, indices = self.index.search(vec, k)
         out = []
         for qi in range(vec.shape[0]):
             row = []
@@ -725,7 +767,8 @@ class FAISS:
 
     def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
                                key: str = "book_id",
-                               mmr: Optional[Tuple[int, float]] = None
+                               mmr: Optional[Tuple[int, float]] = None,
+                               distinct: Optional[str] = None
                                ) -> List[List[Tuple[Document, float]]]:
         """The reference's per-student candidate path
         (candidate_builder.py:138-203) for many students in one device call.
@@ -745,7 +788,15 @@ class FAISS:
         nearest allowed documents by maximal marginal relevance on the device
         (``index.search_mmr`` over the same mean queries and exclusions) and
         returns the first k picks in pick order, so a recommendation list does
-        not fill with near-copies of one book."""
+        not fill with near-copies of one book.
+
+        ``distinct="<metadata field>"`` returns at most one document per value
+        of that field (``distinct="author"``: no author twice per student): the
+        means are computed on the device, come back to the host and are
+        searched by ``index.search_distinct`` with the same exclusions.  Not
+        together with ``mmr``."""
+        if distinct is not None and mmr is not None:
+            raise ValueError("distinct and mmr cannot be combined")
         profiles = list(profiles)
         if exclude is not None:
             exclude = list(exclude)
@@ -754,7 +805,13 @@ class FAISS:
         kept, rows, lists = self.profile_requests(profiles, exclude, key)
         if not kept:
             return out
-        if mmr is not None:
+        if distinct is not None:
+            vec = self.index.mean_rows(rows)
+            if self._normalize_L2:
+                vfaiss.normalize_L2(vec)
+            scores, labels = self.index.search_distinct(vec, k, self._distinct_grouping(distinct),
+                                                        exclude=lists)
+        elif mmr is not None:
             fetch_k, lambda_mult = mmr
             vec = self.index.mean_rows(rows)
             if self._normalize_L2:

@@ -26,6 +26,10 @@ HBM and serves the same vector-store calls to any number of clients:
 * MMR requests (``max_marginal_relevance_search*``, ``recommend_for_profiles``
   with ``mmr=``) run on their own, as ``exact_filter`` requests do: their
   re-rank is part of the engine call (``index.search_mmr``).
+* ``distinct="<metadata field>"`` travels with the search and recommend
+  requests (at most one document per value of the field,
+  ``index.search_distinct``); such requests coalesce with the others of the
+  same k and the same field only.
 * ``RemoteFAISS(address, authkey)`` is the client: the LangChain ``FAISS`` read /
   write surface the reference's call sites use, plus ``.index.ntotal/.d/.search``.
 * Access: the HMAC auth key has no default (the caller supplies a secret);
@@ -114,11 +118,13 @@ class _RWLock:
 
 
 class _Pending:
-    __slots__ = ("vec", "k", "exclude", "done", "D", "I", "err")
+    __slots__ = ("vec", "k", "exclude", "distinct", "done", "D", "I", "err")
 
-    def __init__(self, vec: np.ndarray, k: int, exclude: Optional[Sequence] = None):
+    def __init__(self, vec: np.ndarray, k: int, exclude: Optional[Sequence] = None,
+                 distinct: Optional[str] = None):
         # exclude: one label list per row of vec (None: nothing excluded)
-        self.vec, self.k, self.exclude = vec, k, exclude
+        # distinct: the metadata field of a distinct search (None: a plain one)
+        self.vec, self.k, self.exclude, self.distinct = vec, k, exclude, distinct
         self.done = threading.Event()
         self.D = self.I = self.err = None
 
@@ -127,7 +133,9 @@ class _Coalescer:
     """Stacks concurrent single-query searches into one engine call.
 
     One dispatcher thread: it takes everything queued (up to max_batch rows),
-    groups by k, runs one ``index.search`` per group, and hands each caller its
+    groups by k (and by the field of a distinct search: a request is stacked
+    only with others of its field), runs one ``index.search`` per group, and
+    hands each caller its
     rows.  Callers hold the service's read lock while they wait.  A lone
     request runs at once (no added wait).  Requests may carry one exclusion
     list per row (``index.search(x, k, exclude=...)``): they stack with the
@@ -144,11 +152,11 @@ class _Coalescer:
         self._thread = threading.Thread(target=self._run, name="vsearch-coalescer", daemon=True)
         self._thread.start()
 
-    def submit(self, vec: np.ndarray, k: int,
-               exclude: Optional[Sequence] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def submit(self, vec: np.ndarray, k: int, exclude: Optional[Sequence] = None,
+               distinct: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
         if exclude is not None and len(exclude) != vec.shape[0]:
             raise ValueError("exclude: one label list per query row")
-        p = _Pending(vec, k, exclude)
+        p = _Pending(vec, k, exclude, distinct)
         with self._cv:
             self._queue.append(p)
             self._cv.notify()
@@ -177,19 +185,25 @@ class _Coalescer:
                     rows += p.vec.shape[0]
                 if not take:  # one oversized request: run it alone
                     take = [self._queue.pop(0)]
-            groups: Dict[int, List[_Pending]] = {}
+            groups: Dict[Tuple[int, Optional[str]], List[_Pending]] = {}
             for p in take:
-                groups.setdefault(p.k, []).append(p)
-            for k, ps in groups.items():
+                groups.setdefault((p.k, p.distinct), []).append(p)
+            for (k, distinct), ps in groups.items():
                 try:
                     x = np.concatenate([p.vec for p in ps]) if len(ps) > 1 else ps[0].vec
                     # every submitter holds the read lock while it waits, so no
                     # writer can run during this call
+                    lists: Optional[List[Sequence[int]]] = None
                     if any(p.exclude is not None for p in ps):
-                        lists: List[Sequence[int]] = []
+                        lists = []
                         for p in ps:
                             lists.extend(p.exclude if p.exclude is not None
                                          else [()] * p.vec.shape[0])
+                    if distinct is not None:
+                        store = self._svc.store
+                        D, I = store.index.search_distinct(
+                            x, k, store._distinct_grouping(distinct), exclude=lists)
+                    elif lists is not None:
                         D, I = self._svc.store.index.search(x, k, exclude=lists)
                     else:
                         D, I = self._svc.store.index.search(x, k)
@@ -363,7 +377,8 @@ class IndexService:
                 profiles = [[(v, float(w)) for v, w in p] for p in h["profiles"]]
                 rows = self._read(st.recommend_for_profiles, profiles, int(h.get("k", 4)),
                                   exclude=h.get("exclude"), key=h.get("key", "book_id"),
-                                  mmr=(int(fetch_k), float(lambda_mult)))
+                                  mmr=(int(fetch_k), float(lambda_mult)),
+                                  distinct=h.get("distinct"))
                 return {"results": [[[d.to_json(), float(s)] for d, s in row]
                                     for row in rows]}, b""
             return {"results": self._recommend(h)}, b""
@@ -409,7 +424,7 @@ class IndexService:
                 if st._normalize_L2:
                     from . import faiss as vfaiss
                     vfaiss.normalize_L2(vec)
-                D, I = self._coalescer.submit(vec, int(h.get("k", 4)), lists)
+                D, I = self._coalescer.submit(vec, int(h.get("k", 4)), lists, h.get("distinct"))
                 for j, p in enumerate(kept):
                     out[p] = [[d.to_json(), float(s)] for d, s in st._docs_of_row(D[j], I[j])]
         finally:
@@ -422,6 +437,9 @@ class IndexService:
         st = self.store
         k = int(h.get("k", 4))
         flt = h.get("filter")
+        distinct = h.get("distinct")
+        if distinct is not None and h.get("exact_filter"):
+            raise ValueError("distinct and exact_filter cannot be combined")
         if h.get("exact_filter") and flt is not None:
             # a selector search runs on its own: the coalescer stacks callers
             # that share one k and no selector
@@ -435,7 +453,8 @@ class IndexService:
         docs = []
         self._lock.acquire_read()  # held from the search to the docstore lookup
         try:
-            D, I = self._coalescer.submit(vec, k if flt is None else int(h.get("fetch_k", 20)))
+            D, I = self._coalescer.submit(vec, k if flt is None else int(h.get("fetch_k", 20)),
+                                          None, distinct)
             for s, i in zip(D[0], I[0]):
                 if i == -1:
                     continue
@@ -523,6 +542,13 @@ class RemoteFAISS:
     def _results(h) -> List[Tuple[Document, np.float32]]:
         return [(Document.from_json(d), np.float32(s)) for d, s in h["results"]]
 
+    @staticmethod
+    def _distinct(kwargs) -> dict:
+        """The header entry of ``distinct="<metadata field>"`` (without it the
+        frame is what it always was)."""
+        field = kwargs.get("distinct")
+        return {} if field is None else {"distinct": str(field)}
+
     def _search(self, header: dict, payload: bytes = b""):
         if callable(header.get("filter")):
             raise ValueError("RemoteFAISS: filter must be a dict (callables cannot travel)")
@@ -535,6 +561,7 @@ class RemoteFAISS:
         return self._search({"op": "similarity_search_with_score", "k": k, "filter": filter,
                              "fetch_k": fetch_k, "exact_filter": bool(exact_filter),
                              "score_threshold": kwargs.get("score_threshold"),
+                             **self._distinct(kwargs),
                              "shape": list(v.shape)}, v.astype("<f4").tobytes())
 
     def similarity_search_with_score(self, query: str, k: int = 4, filter=None,
@@ -542,7 +569,8 @@ class RemoteFAISS:
         return self._search({"op": "similarity_search_with_score", "query": query, "k": k,
                              "filter": filter, "fetch_k": fetch_k,
                              "exact_filter": bool(exact_filter),
-                             "score_threshold": kwargs.get("score_threshold")})
+                             "score_threshold": kwargs.get("score_threshold"),
+                             **self._distinct(kwargs)})
 
     def similarity_search_by_vector(self, embedding, k: int = 4, filter=None, fetch_k: int = 20,
                                     exact_filter: bool = False, **kwargs) -> List[Document]:
@@ -579,15 +607,18 @@ class RemoteFAISS:
              "exact_filter": bool(kwargs.get("exact_filter", False))})]
 
     def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None, key: str = "book_id",
-                               mmr: Optional[Tuple[int, float]] = None
+                               mmr: Optional[Tuple[int, float]] = None,
+                               distinct: Optional[str] = None
                                ) -> List[List[Tuple[Document, np.float32]]]:
         """``FAISS.recommend_for_profiles`` on the server; concurrent callers
-        share one engine batch (a request with ``mmr=`` runs on its own)."""
+        share one engine batch (a request with ``mmr=`` runs on its own, one
+        with ``distinct=`` shares a batch with the others of its field)."""
         header = {"op": "recommend_for_profiles", "k": int(k), "key": key,
                   "profiles": [[[v, float(w)] for v, w in p] for p in profiles],
                   "exclude": None if exclude is None else [list(e) for e in exclude]}
         if mmr is not None:  # (without it the frame is what it always was)
             header["mmr"] = [int(mmr[0]), float(mmr[1])]
+        header.update(self._distinct({"distinct": distinct}))
         res = self._call(header)[0]["results"]
         return [[(Document.from_json(d), np.float32(s)) for d, s in row] for row in res]
 

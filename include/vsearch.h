@@ -260,6 +260,71 @@ int vs_search_profiles(vs_index* idx, const int64_t* offs, const int64_t* labels
                        const int64_t* excl_labels, int exclude_profile, float* D, int64_t* I,
                        int flags, void* stream);
 
+/* ---- distinct searches -----------------------------------------------------
+ * The k nearest GROUPS, one best row per group (Qdrant search_groups with
+ * group_size 1, Elasticsearch collapse, Milvus group_by_field).  The reference
+ * appends a second row when a book is re-embedded
+ * (src/incremental_workers/book_vector/main.py:148,
+ * src/ingestion_service/pipeline.py:363), and its callers search k * 2 and
+ * skip the book ids they have seen
+ * (src/recommendation_api/candidate_builder.py:512, service.py:387-399): a
+ * book with many rows near the query swallows any fixed over-fetch.
+ *
+ * A grouping gives every label of an index a group: an int32 >= 0, or -1 for
+ * "this row is its own group".  group_of_label: n HOST int32, entry i the group
+ * of label id_base + i; n must equal the live row count (vs_ntotal), a value
+ * below -1 is VS_E_INVALID (checked before the index is read).  The handle
+ * keeps a device copy and the index's generation: whatever moves rows or
+ * changes labels (vs_add, vs_remove_ids, vs_reset, a pack, vs_set_id_base to
+ * another base) makes it stale. */
+typedef struct vs_grouping vs_grouping;
+int vs_grouping_create(vs_index* idx, const int32_t* group_of_label, int64_t n, void* stream,
+                       vs_grouping** out);
+/* The distinct groups, every -1 row counted as one. */
+int vs_grouping_groups(const vs_grouping* grp, int64_t* out);
+int vs_grouping_destroy(vs_grouping* grp);
+/* For query q take the rows a plain search would rank (the live rows minus q's
+ * exclusion list, excl_offs / excl_labels as vs_search_excl, NULL: none) in
+ * VS_RAW_ORDER: ascending (key, label), key = distance or -score.  A group's
+ * representative is its first row in that order: the best key, the lowest
+ * label among equal keys.  The call returns what vs_search would return on an
+ * index that held only the representatives: faiss's order over them (the
+ * inner-product tie rule unless VS_RAW_ORDER), min(k, groups among the allowed
+ * rows) entries, then (+FLT_MAX | -FLT_MAX, -1) padding; D is the
+ * representative's score as vs_search reports it.  With every row its own
+ * group the result is vs_search's.
+ *
+ * Exact for any grouping: a query is searched in raw order for a window of w
+ * entries; if those hold `need` groups (2k - 1 under the inner-product rule,
+ * else k) their first entries are the `need` best representatives, if they
+ * hold fewer groups but every allowed row there are no more, otherwise the
+ * query alone is searched again with a window four times longer, at last over
+ * every live row (vs_distinct_plan shows the schedule).  A grouping where one
+ * group holds most of a query's nearest rows pays for the long windows: past
+ * 1,023 entries the paged engine answers, about w / 64 passes over the rows.
+ *
+ * Checked before the index is read, in this order: the index, the grouping,
+ * n >= 0, k > 0 (VS_E_INVALID); k > 1024: VS_E_UNSUPPORTED (the collapse's
+ * table holds 2 x 2047 groups); the exclusion offsets; the buffers.  A grouping
+ * of another index or an older generation: VS_E_INVALID ("stale grouping").
+ * flags: VS_RAW_ORDER, VS_IN_DEVICE (x), VS_OUT_DEVICE (D, I).  The call reads
+ * a 4-byte count after every round but the last, so it waits for `stream`; a
+ * capturing stream: VS_E_UNSUPPORTED. */
+int vs_search_distinct(vs_index* idx, const vs_grouping* grp, const float* x, int64_t n, int64_t k,
+                       const int64_t* excl_offs, const int64_t* excl_labels, float* D, int64_t* I,
+                       int flags, void* stream);
+/* Diagnostic (touches no device): the windows of a distinct search for k over
+ * `live` rows, round by round: out[r] for r < nmax; non-decreasing, the last
+ * one equal to `live`.  Returns the number of rounds of the whole schedule
+ * (0 for live == 0), or VS_E_INVALID (k outside 1 .. 1024, a bad metric,
+ * live < 0). */
+int vs_distinct_plan(int64_t k, int metric, int raw, int64_t live, int64_t* out, int nmax);
+/* Process-wide counters of the distinct searches since the last reset
+ * (reset != 0 clears them): queries searched, rounds run (summed over the
+ * calls' chunks of queries), and queries whose first window was too short
+ * (searched again at least once). */
+int vs_distinct_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int reset);
+
 /* ---- MMR searches ----------------------------------------------------------
  * LangChain's maximal-marginal-relevance searches
  * (FAISS.max_marginal_relevance_search*, as_retriever(search_type="mmr")):
