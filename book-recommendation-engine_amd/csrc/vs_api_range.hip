@@ -1,6 +1,6 @@
 // vs_api_range.hip — range searches ("Range search" and "Range
-// self-join"): vs_range_search, vs_range_selfjoin and the vs_range result's
-// exports.
+// self-join"): vs_range_search, vs_range_selfjoin, its row-list form
+// vs_range_selfjoin_rows ("In-place updates") and the vs_range result's exports.
 #include "vs_host.h"
 
 using namespace vs;
@@ -186,12 +186,13 @@ int run_range(vs_index* idx, const vs_selector* sel, const float* x, int64_t n, 
   return VS_OK;
 }
 
-// The join behind vs_range_selfjoin, with the index's lock held and no
-// tombstones in place: queries are rows q0 .. q0 + nq, read where they are
-// stored ("Range self-join").
-int run_range_join(vs_index* idx, int64_t q0, int64_t nq, float min_sim, int exclude_self,
-                   int upper, hipStream_t st, vs_range* r) {
-  const char* who = "vs_range_selfjoin";
+// The join behind vs_range_selfjoin / vs_range_selfjoin_rows, with the index's
+// lock held and no tombstones in place: queries are rows q0 .. q0 + nq, read
+// where they are stored ("Range self-join"), or, with `qrows`
+// (host, nq checked positions), the rows qrows[0 .. nq) gathered into a scratch
+// block of their own ("In-place updates").
+int run_range_join(const char* who, vs_index* idx, int64_t q0, const int64_t* qrows, int64_t nq,
+                   float min_sim, int exclude_self, int upper, hipStream_t st, vs_range* r) {
   const int ntotal = (int)idx->ntotal;
   const int64_t nq_pad = round_up(nq, kBQ);
   Scratch scr(st);
@@ -218,11 +219,30 @@ int run_range_join(vs_index* idx, int64_t q0, int64_t nq, float min_sim, int exc
   VS_HIPW(launch_range_thr(bkey, (int)nq, (int)nq_pad, -min_sim, thr, st, 0), who,
           ": thresholds");
 
+  // the row list's queries: the rows and their inverse norms side by side, as
+  // the window form finds them in place
+  int* dqrows = nullptr;
+  char* qmat = nullptr;
+  float* qinv = nullptr;
+  std::vector<int> hq;
+  if (qrows) {
+    hq.assign(qrows, qrows + nq);
+    VS_HIPW(scr.alloc((void**)&dqrows, (size_t)nq * sizeof(int)), who, ": scratch");
+    VS_HIPW(scr.alloc((void**)&qmat, (size_t)nq_pad * idx->rowbytes()), who, ": scratch");
+    VS_HIPW(scr.alloc((void**)&qinv, (size_t)nq_pad * sizeof(float)), who, ": scratch");
+    VS_HIPW(hipMemcpyAsync(dqrows, hq.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st),
+            who, ": upload");
+    VS_HIPW(launch_range_gather_rows(idx->codes, idx->rowbytes(), rinv, dqrows, (int)nq,
+                                     (int)nq_pad, qmat, qinv, st),
+            who, ": gather");
+  }
+
   RangeJob job;
   job.who = who;
   job.mode = MODE_COS;
-  job.qmat = idx->row(q0);  // capacity keeps kBQ rows of slack (as vs_selfjoin)
-  job.qaux = rinv + q0;
+  // capacity keeps kBQ rows of slack (as vs_selfjoin)
+  job.qmat = qrows ? (const void*)qmat : (const void*)idx->row(q0);
+  job.qaux = qrows ? qinv : rinv + q0;
   job.xaux = rinv;
   job.n = nq;
   job.nq_pad = nq_pad;
@@ -234,10 +254,64 @@ int run_range_join(vs_index* idx, int64_t q0, int64_t nq, float min_sim, int exc
                                 return launch_range_join_verify(
                                     cand, ncand, off, nsplit, (int)nq, idx->codes, idx->esize,
                                     rinv, idx->ld, ntotal, q0, min_sim, exclude_self, upper, ekey,
-                                    flag, st);
+                                    flag, st, dqrows);
                               });
   if (rc) return rc;
   VS_HIPW(hipStreamSynchronize(st), who, ": synchronise");
+  return VS_OK;
+}
+
+// What vs_range_selfjoin and vs_range_selfjoin_rows share once their own
+// arguments are checked: the pack of tombstones (as vs_selfjoin: query rows are
+// read in place and labels are row numbers), the check of the query rows
+// against the rows then in place, the stream, the result handle and the join.
+int range_join_call(const char* who, vs_index* idx, int64_t q0, const int64_t* qrows, int64_t nq,
+                    float min_sim, int exclude_self, int upper, hipStream_t st, vs_range** out) {
+  const std::string w(who);
+  std::shared_lock<std::shared_mutex> lk(idx->mu);
+  while (!idx->dead.empty()) {
+    lk.unlock();
+    {
+      std::unique_lock<std::shared_mutex> wl(idx->mu);
+      const int rc = pack_dead(idx);
+      if (rc) return rc;
+    }
+    lk.lock();
+  }
+  if (!qrows && q0 + nq > idx->ntotal) return fail(VS_E_INVALID, w + ": query rows out of range");
+  for (int64_t i = 0; qrows && i < nq; ++i)
+    if (qrows[i] < 0 || qrows[i] >= idx->ntotal)
+      return fail(VS_E_INVALID, w + ": row " + std::to_string(qrows[i]) + " out of range");
+  DeviceGuard g(idx->device);
+  if (!g.ok) return fail(VS_E_HIP, w + ": hipSetDevice failed");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  VS_HIPW(hipStreamIsCapturing(st, &cs), who, ": stream");
+  if (cs != hipStreamCaptureStatusNone)
+    return fail(VS_E_UNSUPPORTED,
+                w + ": a capturing stream (the call reads its totals on the host)");
+  vs_range* r = new vs_range();
+  r->device = idx->device;
+  r->nq = nq;
+  hipError_t e = hipMalloc(&r->lims, (size_t)(nq + 1) * sizeof(int64_t));
+  if (e != hipSuccess) {
+    delete r;
+    return hip_fail(e, (w + ": lims").c_str());
+  }
+  int rc = VS_OK;
+  if (nq == 0 || idx->ntotal == 0) {
+    e = hipMemsetAsync(r->lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = hip_fail(e, (w + ": lims").c_str());
+  } else {
+    ReaderMark mark(idx, st);
+    rc = run_range_join(who, idx, q0, qrows, nq, min_sim, exclude_self ? 1 : 0, upper ? 1 : 0, st,
+                        r);
+  }
+  if (rc) {
+    free_range(r);
+    return rc;
+  }
+  *out = r;
   return VS_OK;
 }
 
@@ -302,51 +376,23 @@ int vs_range_selfjoin(vs_index* idx, int64_t q0, int64_t nq, float min_sim, int 
   if (q0 < 0 || nq < 0) return fail(VS_E_INVALID, "vs_range_selfjoin: query rows out of range");
   if (nq > 65536)
     return fail(VS_E_UNSUPPORTED, "vs_range_selfjoin: more than 65536 query rows in one call");
-  hipStream_t st = (hipStream_t)stream;
-  // as vs_selfjoin: the query rows are read in place and labels are row
-  // numbers, so tombstones are packed first
-  std::shared_lock<std::shared_mutex> lk(idx->mu);
-  while (!idx->dead.empty()) {
-    lk.unlock();
-    {
-      std::unique_lock<std::shared_mutex> wl(idx->mu);
-      const int rc = pack_dead(idx);
-      if (rc) return rc;
-    }
-    lk.lock();
-  }
-  if (q0 + nq > idx->ntotal)
-    return fail(VS_E_INVALID, "vs_range_selfjoin: query rows out of range");
-  DeviceGuard g(idx->device);
-  if (!g.ok) return fail(VS_E_HIP, "vs_range_selfjoin: hipSetDevice failed");
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  VS_HIP(hipStreamIsCapturing(st, &cs), "vs_range_selfjoin: stream");
-  if (cs != hipStreamCaptureStatusNone)
+  return range_join_call("vs_range_selfjoin", idx, q0, nullptr, nq, min_sim, exclude_self, upper,
+                         (hipStream_t)stream, out);
+}
+
+int vs_range_selfjoin_rows(vs_index* idx, const int64_t* qrows, int64_t nq, float min_sim,
+                           int exclude_self, int flags, void* stream, vs_range** out) {
+  (void)flags;
+  if (!out) return fail(VS_E_INVALID, "vs_range_selfjoin_rows: null output");
+  *out = nullptr;
+  if (!idx) return fail(VS_E_INVALID, "vs_range_selfjoin_rows: null index");
+  if (nq < 0) return fail(VS_E_INVALID, "vs_range_selfjoin_rows: nq < 0");
+  if (nq > 65536)
     return fail(VS_E_UNSUPPORTED,
-                "vs_range_selfjoin: a capturing stream (the call reads its totals on the host)");
-  vs_range* r = new vs_range();
-  r->device = idx->device;
-  r->nq = nq;
-  hipError_t e = hipMalloc(&r->lims, (size_t)(nq + 1) * sizeof(int64_t));
-  if (e != hipSuccess) {
-    delete r;
-    return hip_fail(e, "vs_range_selfjoin: lims");
-  }
-  int rc = VS_OK;
-  if (nq == 0 || idx->ntotal == 0) {
-    e = hipMemsetAsync(r->lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = hip_fail(e, "vs_range_selfjoin: lims");
-  } else {
-    ReaderMark mark(idx, st);
-    rc = run_range_join(idx, q0, nq, min_sim, exclude_self ? 1 : 0, upper ? 1 : 0, st, r);
-  }
-  if (rc) {
-    free_range(r);
-    return rc;
-  }
-  *out = r;
-  return VS_OK;
+                "vs_range_selfjoin_rows: more than 65536 query rows in one call");
+  if (nq > 0 && !qrows) return fail(VS_E_INVALID, "vs_range_selfjoin_rows: null buffer");
+  return range_join_call("vs_range_selfjoin_rows", idx, 0, qrows, nq, min_sim, exclude_self, 0,
+                         (hipStream_t)stream, out);
 }
 
 int vs_range_size(const vs_range* r, int64_t* nq, int64_t* total) {

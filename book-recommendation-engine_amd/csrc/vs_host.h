@@ -31,7 +31,8 @@ struct vs_index {
   int64_t capacity = 0;  // rows allocated (multiple of kRowPad, >= ntotal + 256)
   int64_t id_base = 0;
   // bumped by whatever moves rows or changes labels (add, remove_ids, reset, a
-  // tombstone pack, set_id_base): a selector built before is stale
+  // tombstone pack, set_id_base): a selector built before is stale.  An
+  // in-place update (vs_update_rows) does neither and leaves it.
   uint64_t gen = 0;
   char* codes = nullptr;   // [capacity][ld] elements
   int64_t rowbytes() const { return ld * esize; }

@@ -490,6 +490,26 @@ hipError_t launch_gather_kept(const void* X, const float* norms, int64_t rowbyte
                               int64_t n, const int64_t* removed, int64_t nrem, void* tmp,
                               float* tmp_norms, hipStream_t st);
 
+// In-place updates (vs_update.hip; vs_api_update.hip vs_update_rows): staged
+// row i of every array an index holds -> row rows[i] (device, n distinct rows
+// inside the destination arrays).  The staged planes are tile-major over rows
+// [0, n) (plane_offset) like the index's, ldb bytes per row; a null
+// destination leaves that array out.  Scalars: norms, fscale, rn2[2], anorm,
+// anorm_b, one float per row each.
+struct UpdateScatter {
+  const char* s_codes = nullptr;  // [n][rowbytes]
+  char* codes = nullptr;
+  int64_t rowbytes = 0;           // a multiple of 16
+  const char* s_plane[2] = {nullptr, nullptr};
+  char* plane[2] = {nullptr, nullptr};
+  int64_t ldb[2] = {0, 0};        // multiples of 64
+  static constexpr int kScalars = 6;
+  const float* s_scal[kScalars] = {};
+  float* scal[kScalars] = {};
+};
+hipError_t launch_update_scatter(const UpdateScatter& a, const int64_t* rows, int64_t n,
+                                 hipStream_t st);
+
 // Selector searches (vs_select.hip; vs_api_select.hip vs_selector_create / vs_search_sel).
 // A selector is a bitmap over the rows in place (word r >> 5, bit r & 31) and
 // the ascending list of the selected rows.
@@ -577,6 +597,13 @@ hipError_t launch_range_join_verify(const int* cand, int64_t total, const int64_
                                     int nq, const void* X, int xesize, const float* rinv,
                                     int64_t ld, int ntotal, int64_t q0, float min_sim,
                                     int exclude_self, int upper, float* ekey, uint8_t* flag,
+                                    hipStream_t st, const int* qrows = nullptr);
+// The row-list join's queries: row i < nq of Q (rows of rowbytes, a multiple of
+// 16) = row qrows[i] of X and qaux[i] = rinv[qrows[i]]; zero rows / 0 for the
+// padding slots [nq, nq_pad).  With `qrows` (device, nq entries),
+// launch_range_join_verify's query q is row qrows[q] instead of q0 + q.
+hipError_t launch_range_gather_rows(const void* X, int64_t rowbytes, const float* rinv,
+                                    const int* qrows, int nq, int nq_pad, void* Q, float* qaux,
                                     hipStream_t st);
 // hits[q] = the flags set among query q's candidates.
 hipError_t launch_range_hits(const uint8_t* flag, const int64_t* off, int nsplit, int nq,

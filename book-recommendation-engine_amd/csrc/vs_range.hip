@@ -482,7 +482,7 @@ __global__ __launch_bounds__(256) void range_join_verify_kernel(
     const int* __restrict__ cand, int64_t total, const int64_t* __restrict__ off, int nsplit,
     int nq, const RT* __restrict__ X, const float* __restrict__ rinv, int64_t ld, int ntotal,
     int q0, float min_sim, int exclude_self, int upper, float* __restrict__ ekey,
-    uint8_t* __restrict__ flag) {
+    uint8_t* __restrict__ flag, const int* __restrict__ qrows) {
   const int lane = threadIdx.x & 63;
   const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= total) return;
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void range_join_verify_kernel(
     if (off[(int64_t)mid * nsplit] <= c) lo = mid;
     else hi = mid - 1;
   }
-  const int qr = q0 + lo;
+  const int qr = qrows ? qrows[lo] : q0 + lo;  // the row-list join: any row, any order
   const int r = cand[c];
   bool live = r >= 0 && r < ntotal;
   if (exclude_self) live = live && r != qr;
@@ -516,20 +516,55 @@ hipError_t launch_range_join_verify(const int* cand, int64_t total, const int64_
                                     int nq, const void* X, int xesize, const float* rinv,
                                     int64_t ld, int ntotal, int64_t q0, float min_sim,
                                     int exclude_self, int upper, float* ekey, uint8_t* flag,
-                                    hipStream_t st) {
+                                    hipStream_t st, const int* qrows) {
   if (total <= 0) return hipSuccess;
   if (nq < 1 || nsplit < 1 || ld % 4 != 0 || (xesize != 4 && xesize != 2) || total > INT_MAX ||
-      !rinv || q0 < 0 || q0 + nq > ntotal)
+      !rinv || q0 < 0 || (qrows ? upper != 0 : q0 + nq > ntotal))
     return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)((total + 3) / 4);
   if (xesize == 4)
     hipLaunchKernelGGL(range_join_verify_kernel<float>, dim3(blocks), dim3(256), 0, st, cand, total,
                        off, nsplit, nq, (const float*)X, rinv, ld, ntotal, (int)q0, min_sim,
-                       exclude_self, upper, ekey, flag);
+                       exclude_self, upper, ekey, flag, qrows);
   else
     hipLaunchKernelGGL(range_join_verify_kernel<uint16_t>, dim3(blocks), dim3(256), 0, st, cand,
                        total, off, nsplit, nq, (const uint16_t*)X, rinv, ld, ntotal, (int)q0,
-                       min_sim, exclude_self, upper, ekey, flag);
+                       min_sim, exclude_self, upper, ekey, flag, qrows);
+  return hipGetLastError();
+}
+
+// The row-list join's query block: one wave per slot, 16-byte pieces; slot i <
+// nq takes row qrows[i] and its inverse norm, the padding slots zeros (their
+// thresholds are NaN: they admit nothing).
+__global__ __launch_bounds__(256) void range_gather_rows_kernel(
+    const char* __restrict__ X, int64_t rowbytes, const float* __restrict__ rinv,
+    const int* __restrict__ qrows, int nq, int nq_pad, char* __restrict__ Q,
+    float* __restrict__ qaux) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= nq_pad) return;
+  char* dst = Q + (int64_t)i * rowbytes;
+  if (i < nq) {
+    const int r = qrows[i];
+    const char* src = X + (int64_t)r * rowbytes;
+    for (int64_t b = (int64_t)lane * 16; b < rowbytes; b += 1024)
+      *(uint4*)(dst + b) = *(const uint4*)(src + b);
+    if (lane == 0) qaux[i] = rinv[r];
+  } else {
+    for (int64_t b = (int64_t)lane * 16; b < rowbytes; b += 1024)
+      *(uint4*)(dst + b) = make_uint4(0u, 0u, 0u, 0u);
+    if (lane == 0) qaux[i] = 0.0f;
+  }
+}
+
+hipError_t launch_range_gather_rows(const void* X, int64_t rowbytes, const float* rinv,
+                                    const int* qrows, int nq, int nq_pad, void* Q, float* qaux,
+                                    hipStream_t st) {
+  if (nq < 1 || nq_pad < nq || rowbytes <= 0 || rowbytes % 16 != 0 || !X || !rinv || !qrows ||
+      !Q || !qaux)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(range_gather_rows_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0,
+                     st, (const char*)X, rowbytes, rinv, qrows, nq, nq_pad, (char*)Q, qaux);
   return hipGetLastError();
 }
 

@@ -48,6 +48,7 @@ SIGNATURES = {
     "vs_destroy": (_c_int, [_vp]),
     "vs_reserve": (_c_int, [_vp, _c_i64]),
     "vs_add": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp]),
+    "vs_update_rows": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _vp]),
     "vs_add_synthetic": (_c_int, [_vp, _c_i64, ctypes.c_uint64, _c_i64, _vp]),
     "vs_add_synthetic_ids": (_c_int, [_vp, _vp, _c_i64, ctypes.c_uint64, _vp]),
     "vs_reset": (_c_int, [_vp]),
@@ -93,6 +94,8 @@ SIGNATURES = {
     ),
     "vs_range_selfjoin": (_c_int, [_vp, _c_i64, _c_i64, ctypes.c_float, _c_int, _c_int, _c_int, _vp,
                                    ctypes.POINTER(_vp)]),
+    "vs_range_selfjoin_rows": (_c_int, [_vp, _vp, _c_i64, ctypes.c_float, _c_int, _c_int, _vp,
+                                        ctypes.POINTER(_vp)]),
     "vs_merge_topk": (
         _c_int,
         [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _vp],

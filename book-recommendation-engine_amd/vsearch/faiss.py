@@ -493,6 +493,20 @@ class IndexFlat(Index):
         _lib.check(self._lib.vs_add(self._h, ctypes.c_void_p(ptr), int(n), _lib.IN_DEVICE,
                                     ctypes.c_void_p(stream)), "vs_add")
 
+    def update(self, labels, x) -> None:
+        """In-place update (no faiss equivalent; faiss-cpu users remove and
+        add): the live row with label ``labels[i]`` takes the value ``x[i]``,
+        exactly as if it had been added there.  Rows do not move and labels do
+        not change, so ``Selector`` and ``Grouping`` handles stay valid.  A
+        label that is not live, or one given twice, raises and leaves the
+        index unchanged."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        x = _as_f32_rows(x, self._d)
+        if x.shape[0] != labels.size:
+            raise ValueError(f"update: {labels.size} labels for {x.shape[0]} vectors")
+        _lib.check(self._lib.vs_update_rows(self._h, labels.ctypes.data, x.ctypes.data,
+                                            labels.size, 0, None), "vs_update_rows")
+
     def add_synthetic(self, n: int, seed: int, row0: int = 0, stream: int = 0) -> None:
         """Append the counter-based synthetic rows row0..row0+n-1 (see vsearch.synth)."""
         _lib.check(self._lib.vs_add_synthetic(self._h, int(n), ctypes.c_uint64(seed),
@@ -948,8 +962,19 @@ class IndexFlat(Index):
                                          0, None), "vs_selfjoin")
         return S, I
 
+    def _range_join_rows_call(self, rows, min_sim, exclude_self):
+        """One vs_range_selfjoin_rows call: (lims int64 (len(rows)+1), S, I)."""
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.vs_range_selfjoin_rows(self._h, rows.ctypes.data, rows.size,
+                                                    ctypes.c_float(min_sim),
+                                                    1 if exclude_self else 0, 0, None,
+                                                    ctypes.byref(h)),
+                   "vs_range_selfjoin_rows")
+        return self._range_take(h)
+
     def range_selfjoin(self, min_sim, *, q0: int = 0, nq: int | None = None,
-                       exclude_self: bool = True, upper: bool = False, chunk: int = 65536):
+                       exclude_self: bool = True, upper: bool = False, chunk: int = 65536,
+                       rows=None):
         """Cosine range self-join over stored rows [q0, q0+nq): every row whose
         similarity with the query row is >= ``min_sim``, as many as there are
         (``selfjoin`` without its k).  Returns (lims uint64 (nq+1), S float32,
@@ -961,11 +986,26 @@ class IndexFlat(Index):
         each query row q, only the rows r > q — each unordered pair once, for
         about half the work — whether or not ``exclude_self`` is set (a row is
         never after itself).  Zero-norm rows and a NaN ``min_sim`` match
-        nothing.  One C call per ``chunk`` query rows (at most 65536)."""
-        q0 = int(q0)
-        nq = self.ntotal - q0 if nq is None else int(nq)
+        nothing.  One C call per ``chunk`` query rows (at most 65536).
+
+        ``rows=`` gives the query rows as a list of row positions instead of a
+        window (any order, duplicates allowed; exclusive with ``q0`` / ``nq`` /
+        ``upper=True``): entry i's hits are segment i, bit for bit the segment
+        of the single-row window ``q0=rows[i], nq=1``."""
         chunk = int(chunk)
         assert 0 < chunk <= 65536
+        if rows is not None:
+            if q0 != 0 or nq is not None or upper:
+                raise ValueError("range_selfjoin: rows= excludes q0, nq and upper=True")
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            if rows.size == 0:
+                return (np.zeros(1, dtype=np.uint64), np.empty(0, dtype=np.float32),
+                        np.empty(0, dtype=np.int64))
+            parts = [self._range_join_rows_call(rows[c0:c0 + chunk], float(min_sim), exclude_self)
+                     for c0 in range(0, rows.size, chunk)]
+            return self._range_concat(parts, rows.size)
+        q0 = int(q0)
+        nq = self.ntotal - q0 if nq is None else int(nq)
         min_sim = float(min_sim)
         if nq <= 0:
             if nq < 0:

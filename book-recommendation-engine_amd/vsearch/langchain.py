@@ -312,13 +312,22 @@ class FAISS:
 
     def upsert_embeddings(self, texts: Sequence[str], embeddings: Sequence[List[float]],
                           metadatas: Sequence[dict], key: str = "book_id",
-                          ids: Optional[List[str]] = None) -> List[str]:
+                          ids: Optional[List[str]] = None, in_place: bool = False) -> List[str]:
         """Delete-then-add.  The reference appends a second row when a
         book is re-embedded (incremental_workers/book_vector/main.py:148,
         ingestion_service/pipeline.py:363), so searches return the stale copy too.
         Here every existing row whose metadata[key] matches an incoming row is
         removed first (one remove_ids compaction on the device), and within the
-        batch the last row for a key wins.  Rows without the key are plain appends."""
+        batch the last row for a key wins.  Rows without the key are plain appends.
+
+        ``in_place=True``: a key that has a stored row keeps that row's label —
+        its vector is replaced where it is (``index.update``; no compaction)
+        and its document by the new one, under the id a plain add would have
+        given it.  A key with several rows keeps the lowest label, the others
+        are deleted; a key without a row is appended.  A batch of pure
+        re-embeddings (nothing appended or deleted, every replaced document's
+        metadata equal to the old one's) keeps the cached ``filter=`` selectors
+        and ``distinct=`` groupings."""
         texts, embeddings, metadatas = list(texts), list(embeddings), list(metadatas)
         _len_check_if_sized(texts, metadatas, "texts", "metadatas")
         _len_check_if_sized(texts, embeddings, "texts", "embeddings")
@@ -335,19 +344,80 @@ class FAISS:
             clash.difference_update(stale)
             if clash:
                 raise ValueError(f"Tried to add ids that already exist: {clash}")
+        if in_place:
+            return self._upsert_in_place(texts, embeddings, metadatas, key, ids, keep)
         if stale:
             self.delete(stale)
         return self.__add([texts[j] for j in keep], [embeddings[j] for j in keep],
                           metadatas=[metadatas[j] for j in keep],
                           ids=None if ids is None else [ids[j] for j in keep])
 
+    def _upsert_in_place(self, texts, embeddings, metadatas, key, ids, keep) -> List[str]:
+        """``upsert_embeddings(in_place=True)`` after its checks: `keep` = the
+        batch's rows that count (the last one per key)."""
+        if not hasattr(self.index, "update"):
+            raise ValueError("upsert with in_place=True needs an index with update(labels, x) "
+                             f"(vsearch.faiss.IndexFlat); {type(self.index).__name__} has none")
+        if not hasattr(self.docstore, "add"):
+            raise ValueError("If trying to add texts, the underlying docstore should support "
+                             f"adding items, which {self.docstore} does not")
+        new_ids = {j: (ids[j] if ids is not None else str(uuid.uuid4())) for j in keep}
+        if len(set(new_ids.values())) != len(new_ids):
+            raise ValueError("Duplicate ids found in the ids list.")
+        keylabels = self._key_labels(key)  # kept across pure re-embeddings
+        replace, append, extra = [], [], []
+        for j in keep:
+            value = metadatas[j].get(key)
+            labels = keylabels.get(value) if value is not None else None
+            if labels:
+                replace.append((j, labels[0]))
+                extra.extend(self.index_to_docstore_id[i] for i in labels[1:])
+            else:
+                append.append(j)
+        changed = False
+        if replace:
+            vector = np.array([embeddings[j] for j, _ in replace], dtype=np.float32)
+            if vector.ndim == 1:
+                vector = vector.reshape(len(replace), -1)
+            if self._normalize_L2:
+                vfaiss.normalize_L2(vector)
+            self.index.update(np.array([i for _, i in replace], dtype=np.int64), vector)
+            for j, label in replace:
+                old_id = self.index_to_docstore_id[label]
+                old = self.docstore.search(old_id)
+                if not isinstance(old, Document) or old.metadata != metadatas[j]:
+                    changed = True
+                new_id = new_ids[j]
+                self.docstore.delete([old_id])
+                self.docstore.add({new_id: Document(id=new_id, page_content=texts[j],
+                                                    metadata=metadatas[j])})
+                self.index_to_docstore_id[label] = new_id
+                # _key_labels indexed `key`: the old and the new document share its value
+                lst = self._keymap.get(metadatas[j][key])
+                if lst is not None and old_id in lst:
+                    lst[lst.index(old_id)] = new_id
+        if changed:  # a filter or a grouping may read the fields that changed
+            self._sel_cache.clear()
+            self._grp_cache.clear()
+            self._keylabels = None
+        if extra:  # after the update: a delete renumbers the labels
+            self.delete(extra)
+        if append:
+            self.__add([texts[j] for j in append], [embeddings[j] for j in append],
+                       metadatas=[metadatas[j] for j in append],
+                       ids=[new_ids[j] for j in append])
+        return [new_ids[j] for j in keep]
+
     def upsert_texts(self, texts: Iterable[str], metadatas: List[dict], key: str = "book_id",
-                     ids: Optional[List[str]] = None, **kwargs: Any) -> List[str]:
-        """`add_texts` with delete-then-add on metadata[key]; embeds before mutating,
-        so an embedding failure leaves the store unchanged."""
+                     ids: Optional[List[str]] = None, in_place: bool = False,
+                     **kwargs: Any) -> List[str]:
+        """`add_texts` with delete-then-add on metadata[key] (or, with
+        ``in_place=True``, ``upsert_embeddings``'s replacement in place); embeds
+        before mutating, so an embedding failure leaves the store unchanged."""
         texts = list(texts)
         embeddings = self._embed_documents(texts)
-        return self.upsert_embeddings(texts, embeddings, metadatas, key=key, ids=ids)
+        return self.upsert_embeddings(texts, embeddings, metadatas, key=key, ids=ids,
+                                      in_place=in_place)
 
     def delete(self, ids: Optional[List[str]] = None, **kwargs: Any) -> Optional[bool]:
         if ids is None:

@@ -389,7 +389,8 @@ class IndexService:
                                        ids=h.get("ids"))}, b""
         if op == "upsert_texts":
             return {"ids": self._write(st.upsert_texts, h["texts"], h["metadatas"],
-                                       key=h.get("key", "book_id"), ids=h.get("ids"))}, b""
+                                       key=h.get("key", "book_id"), ids=h.get("ids"),
+                                       in_place=bool(h.get("in_place", False)))}, b""
         if op == "delete":
             return {"result": self._write(st.delete, h["ids"])}, b""
         if op == "get_by_ids":
@@ -633,9 +634,10 @@ class RemoteFAISS:
                            "ids": ids})[0]["ids"]
 
     def upsert_texts(self, texts, metadatas: List[dict], key: str = "book_id",
-                     ids: Optional[List[str]] = None, **kwargs) -> List[str]:
+                     ids: Optional[List[str]] = None, in_place: bool = False,
+                     **kwargs) -> List[str]:
         return self._call({"op": "upsert_texts", "texts": list(texts), "metadatas": metadatas,
-                           "key": key, "ids": ids})[0]["ids"]
+                           "key": key, "ids": ids, "in_place": bool(in_place)})[0]["ids"]
 
     def delete(self, ids: Optional[List[str]] = None, **kwargs) -> Optional[bool]:
         if ids is None:

@@ -21,6 +21,12 @@ every neighbour past the 15th.  ``student_edges`` / ``StudentIndex.edges`` /
 (``vs_range_selfjoin``), as many rows as pass.  The top-15 forms above remain
 the drop-in replacement.
 
+A re-embedded student (student_embedding/main.py:137-145 upserts the vector,
+the similarity worker then recomputes that student's rows) is
+``StudentIndex.replace`` — the vector changes where it is stored — and a batch
+of them ``StudentIndex.reembed``: one in-place update, one row-list join, and
+the rows that name an updated student, which are the graph's complete diff.
+
 Semantics notes: ties (equal similarity) are ordered by lower row; SQL leaves
 them unspecified.  Zero-norm vectors never match; pgvector returns NaN for them
 and the refresher's ``sim >= threshold`` test drops NaN too.
@@ -159,6 +165,65 @@ class StudentIndex:
         q = self._row[student]
         lims, S, I = self.index.range_selfjoin(float(threshold), q0=q, nq=1, exclude_self=True)
         return _edge_rows(self.keys, lims, S, I, q, True, False)
+
+    def edges_of_many(self, students: Sequence[str],
+                      threshold: float = DEFAULT_THRESHOLD) -> List[Tuple[str, str, float]]:
+        """``edges_of`` for a list of students in one row-list join (one pass
+        over the rows per 128 students, not one per student): each student's
+        rows in list order, ordered by the neighbour's position."""
+        rows = np.array([self._row[s] for s in students], dtype=np.int64)
+        if rows.size == 0:
+            return []
+        lims, S, I = self.index.range_selfjoin(float(threshold), rows=rows, exclude_self=True)
+        counts = np.diff(np.asarray(lims).astype(np.int64))
+        a = np.repeat(rows, counts)
+        return [(self.keys[int(x)], self.keys[int(y)], float(v)) for x, y, v in zip(a, I, S)]
+
+    def _prepare(self, vectors) -> np.ndarray:
+        v = np.asarray(vectors, dtype=np.float32).reshape(-1, self.index.d)
+        return pgvector_quantize(v) if self.quantize else np.ascontiguousarray(v)
+
+    def replace(self, student: str, vector) -> None:
+        """Replace one student's vector in place (the ``ON CONFLICT ... DO
+        UPDATE SET vec`` of student_embedding/main.py:137-145): no row moves,
+        keys and positions stay.  An unknown student raises ``KeyError``."""
+        r = self._row[student]
+        self.index.update(np.array([r], dtype=np.int64), self._prepare(vector))
+
+    def reembed(self, updates, threshold: float = DEFAULT_THRESHOLD
+                ) -> List[Tuple[str, str, float]]:
+        """Re-embed a batch of students and return their diff of the graph.
+
+        ``updates``: a mapping student -> vector or a list of (student,
+        vector), every student known (``KeyError`` otherwise, before anything
+        changes) and named once.  One in-place ``update``, then one row-list
+        join.  Returns the directed (a, b, sim) rows that name an updated
+        student — (u, r) and the mirrored (r, u), a pair of two updated
+        students once per direction — ordered by a's position, then b's.  The
+        caller deletes every ``student_similarity`` row naming an updated
+        student and inserts these (the similarity is the same bits in both
+        directions, so the updated students' edges are the complete diff)."""
+        items = list(updates.items()) if hasattr(updates, "items") else list(updates)
+        if not items:
+            return []
+        rows = np.array([self._row[s] for s, _ in items], dtype=np.int64)
+        if np.unique(rows).size != rows.size:
+            raise ValueError("StudentIndex.reembed: a student named twice")
+        self.index.update(rows, self._prepare([v for _, v in items]))
+        lims, S, I = self.index.range_selfjoin(float(threshold), rows=rows, exclude_self=True)
+        counts = np.diff(np.asarray(lims).astype(np.int64))
+        u = np.repeat(rows, counts)
+        r = np.asarray(I, dtype=np.int64)
+        s = np.asarray(S, dtype=np.float32)
+        # (u, r) as found; (r, u) mirrored unless r is updated too (its own
+        # segment holds that direction already)
+        other = ~np.isin(r, rows)
+        a = np.concatenate([u, r[other]])
+        b = np.concatenate([r, u[other]])
+        s = np.concatenate([s, s[other]])
+        order = np.lexsort((b, a))
+        return [(self.keys[int(x)], self.keys[int(y)], float(v))
+                for x, y, v in zip(a[order], b[order], s[order])]
 
     def upsert(self, student: str, vector) -> None:
         """Insert or replace one student's vector (a removed row compacts the

@@ -90,6 +90,35 @@ int vs_reserve(vs_index* idx, int64_t n);
  * src/incremental_workers/book_vector/main.py:148. */
 int vs_add(vs_index* idx, const float* x, int64_t n, int flags, void* stream);
 
+/* In-place update: the live row with label labels[i] takes the value x[i]
+ * (n * d float32), exactly as if that value had been added there: fp32 indexes
+ * store the bits given, bf16 indexes the round-to-nearest-even value vs_add
+ * would store, and every derived byte (norms, filter planes, scales, residual
+ * and augmented norms) is the one vs_add derives.  Replaces remove-then-add
+ * for the reference's upserts (student_embedding/main.py:137-145 ON CONFLICT
+ * DO UPDATE; the re-embedding of a book, book_vector/main.py:148).
+ *
+ * labels is HOST int64 (id_base applied); VS_IN_DEVICE covers x only.  A label
+ * is mapped to its row in place through the tombstone list, so an index with
+ * unpacked removals works.  Checked before anything is written, in this order
+ * (on failure the index is unchanged): the index, n >= 0, the buffers; every
+ * label is a live label (VS_E_INVALID otherwise, the labels faiss reconstruct
+ * throws for); no label is given twice (VS_E_INVALID).  n == 0 is success.
+ *
+ * No row moves and no label changes, so the index's generation stays: a
+ * selector or a grouping built before the call stays valid and sees the new
+ * values.  The call waits for the searches of this index already enqueued
+ * (as a storage growth in vs_add does) and returns after `stream` is
+ * synchronised, as vs_add: the caller may free x.  Its cost does not depend on
+ * the rows the index holds (but for the O(removed) walk that maps labels).
+ *
+ * The bound maxima of the filter planes only grow here: they may stay higher
+ * than a fresh index's until vs_remove_ids recomputes them.  A maximum that is
+ * too high is still a bound: results do not change, only how early a query is
+ * settled. */
+int vs_update_rows(vs_index* idx, const int64_t* labels, const float* x, int64_t n, int flags,
+                   void* stream);
+
 /* Appends n rows of the deterministic counter-based synthetic corpus
  * (row r = global row row0 + i; see vs_fill_synthetic).  Benchmark/test feed only. */
 int vs_add_synthetic(vs_index* idx, int64_t n, uint64_t seed, int64_t row0, void* stream);
@@ -188,7 +217,8 @@ int vs_search(vs_index* idx, const float* x, int64_t n, int64_t k, float* D, int
  * ((l - id_base) & 7) of byte ((l - id_base) >> 3) is set; nbits bits are
  * given, labels past nbits or past ntotal are not selected.  Anything that
  * moves rows or changes labels (vs_add, vs_remove_ids, vs_reset,
- * vs_set_id_base to another base) makes the selector stale. */
+ * vs_set_id_base to another base) makes the selector stale.  vs_update_rows
+ * does neither: a selector stays valid across it. */
 typedef struct vs_selector vs_selector;
 int vs_selector_create(vs_index* idx, const uint8_t* bitmap, int64_t nbits, void* stream,
                        vs_selector** out);
@@ -276,7 +306,8 @@ int vs_search_profiles(vs_index* idx, const int64_t* offs, const int64_t* labels
  * below -1 is VS_E_INVALID (checked before the index is read).  The handle
  * keeps a device copy and the index's generation: whatever moves rows or
  * changes labels (vs_add, vs_remove_ids, vs_reset, a pack, vs_set_id_base to
- * another base) makes it stale. */
+ * another base) makes it stale.  vs_update_rows does neither: a grouping
+ * stays valid across it. */
 typedef struct vs_grouping vs_grouping;
 int vs_grouping_create(vs_index* idx, const int32_t* group_of_label, int64_t n, void* stream,
                        vs_grouping** out);
@@ -473,6 +504,19 @@ int vs_selfjoin(vs_index* idx, int64_t q0, int64_t nq, int64_t k, int exclude_se
  * the query rows).  flags: none yet (pass 0). */
 int vs_range_selfjoin(vs_index* idx, int64_t q0, int64_t nq, float min_sim, int exclude_self,
                       int upper, int flags, void* stream, vs_range** out);
+
+/* vs_range_selfjoin with the query rows given as a list: qrows is HOST int64,
+ * nq row positions in any order, duplicates allowed; entry i gets segment i of
+ * lims.  The exact key, the not-strict comparison, the zero-norm rule, the
+ * pack of tombstones first, the 65536-row and 2^31 limits, the refusal of a
+ * capturing stream and the result handle are vs_range_selfjoin's: a segment is
+ * bit-identical to the one vs_range_selfjoin(q0 = row, nq = 1) returns, and
+ * symmetry holds.  A position outside [0, ntotal), checked after the pack, is
+ * VS_E_INVALID.  There is no `upper` (the triangle needs a window).  One pass
+ * over the rows serves 128 listed rows: the edges of a batch of re-embedded
+ * students (vs_update_rows) are its complete diff of the graph. */
+int vs_range_selfjoin_rows(vs_index* idx, const int64_t* qrows, int64_t nq, float min_sim,
+                           int exclude_self, int flags, void* stream, vs_range** out);
 
 /* Merge nparts per-shard top-k lists into one (faiss: the ResultHandler merge;
  * GPU-side half of the RCCL all-gather top-k merge).  Inputs are DEVICE arrays
