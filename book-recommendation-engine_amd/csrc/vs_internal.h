@@ -681,4 +681,62 @@ hipError_t launch_distinct_collapse(int mode, const float* Din, const int64_t* I
 hipError_t launch_distinct_scatter(const float* Din, const int64_t* Iin, int ns, int k,
                                    const int* qmap, float* Dout, int64_t* Iout, hipStream_t st);
 
+// Example searches (vs_examples.hip; vs_api_examples.hip vs_search_examples).
+constexpr int kExamplesMaxK = 1024;   // the emit sorts 2 x 1024 packed keys in LDS
+constexpr int kExamplesMaxList = 64;  // positives, and negatives, of one user
+// out[i][0 .. d) = row rows[i] (in place) as fp32, bf16 widened exactly.
+hipError_t launch_examples_gather(const void* X, int esize, int64_t ld, int d, const int64_t* rows,
+                                  int64_t n, float* out, hipStream_t st);
+// One user of a round's batch.
+struct ExamplesUser {
+  int pos0 = 0;      // the first of its positives' slots in the round's windows
+  int a = 0;         // positives (1 .. kExamplesMaxList)
+  int neg0 = 0;      // the first of its negatives' rows in the staged negatives
+  int b = 0;         // negatives (0 .. kExamplesMaxList)
+  int out = 0;       // its row of D / I / E and of the unsettled flags
+  int tbits = 0;     // its table holds 1 << tbits slots, at least 2 a w
+  int64_t toff = 0;  // the table's first slot in trow / tval
+  int64_t coff = 0;  // its first candidate slot in ckey / cpos (a w of them)
+};
+// A round's windows -> the users' answers (the unit's header): Din / Iin
+// [slots][w] raw entries (labels = row + id_base, -1 after the end); trow (all
+// bytes 0xFF) / tval (all bytes 0xFF) the tables, ccount (zeroed) [nu], F [nu],
+// ckey / cpos the candidates; X / xn the index's rows and norms, Qp / qp the
+// round's positives (fp32 rows of stride ld, by slot) and their |e|^2 (L2),
+// Qn / qn the staged negatives likewise.  Writes rows `out` of D / I / E
+// ([..][k]) and unsettled[out]; *err = 1 if a table or a candidate list
+// overflowed (the sizes above make that impossible; the call must fail).
+struct ExamplesCollapse {
+  int mode = MODE_IP;
+  const ExamplesUser* users = nullptr;  // device, nu entries
+  int nu = 0, amax = 0, tbits_max = 0;  // the batch's longest list and largest table
+  bool any_neg = false;                 // some user of the batch has negatives
+  const float* Din = nullptr;
+  const int64_t* Iin = nullptr;
+  int w = 0;
+  bool w_is_all = false;
+  int64_t id_base = 0;
+  int* trow = nullptr;
+  unsigned long long* tval = nullptr;
+  unsigned long long* F = nullptr;
+  int* ccount = nullptr;
+  unsigned long long* ckey = nullptr;
+  int* cpos = nullptr;
+  int* err = nullptr;
+  const void* X = nullptr;
+  int xesize = 4;
+  const float* xn = nullptr;
+  const float* Qp = nullptr;  // the round's positives, by slot
+  const float* qp = nullptr;
+  const float* Qn = nullptr;
+  const float* qn = nullptr;
+  int64_t ld = 0;
+  int k = 0;
+  float* D = nullptr;
+  int64_t* I = nullptr;
+  int* E = nullptr;
+  int* unsettled = nullptr;
+};
+hipError_t launch_examples_collapse(const ExamplesCollapse& c, hipStream_t st);
+
 }  // namespace vs

@@ -76,6 +76,11 @@ SIGNATURES = {
                                     _vp]),
     "vs_distinct_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _vp, _c_int]),
     "vs_distinct_stats": (_c_int, [_i64p, _i64p, _i64p, _c_int]),
+    "vs_search_examples": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
+                                    _vp, _vp, _c_int, _vp]),
+    "vs_search_examples_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp,
+                                      _vp, _c_int, _vp]),
+    "vs_examples_stats": (_c_int, [_i64p, _i64p, _i64p, _c_int]),
     "vs_mmr_select": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_double, _vp, _c_int,
                                _vp]),
     "vs_search_mmr": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, ctypes.c_double, _vp, _vp, _vp,

@@ -71,6 +71,8 @@ __all__ = [
     "selector_bitmap",
     "exclusion_csr",
     "profile_csr",
+    "examples_csr",
+    "examples_stats",
     "gather_picks",
     "normalize_L2",
     "read_index",
@@ -269,6 +271,50 @@ def profile_csr(profiles):
     weights = np.concatenate(wts) if n else np.zeros(0, dtype=np.float32)
     return (offs, np.ascontiguousarray(labels, dtype=np.int64),
             np.ascontiguousarray(weights, dtype=np.float32))
+
+
+def examples_csr(examples, n: int | None = None, d: int | None = None):
+    """Per-user example lists as a CSR for ``search_examples``: ``(offs, labels,
+    vectors)`` with offs int64 (n + 1) and exactly one of labels (int64) and
+    vectors (float32, (offs[-1], d)) not None.
+
+    ``examples`` is a sequence of per-user lists of labels, or of per-user 2-D
+    float arrays (the vector form; an empty list may stand for a user without
+    examples in either form).  ``None`` is n empty label lists."""
+    if examples is None:
+        if n is None:
+            raise ValueError("examples: None needs the number of users")
+        return np.zeros(int(n) + 1, dtype=np.int64), np.zeros(0, dtype=np.int64), None
+    items = list(examples)
+    if n is not None and len(items) != int(n):
+        raise ValueError(f"examples: expected {int(n)} lists, got {len(items)}")
+    vec = [isinstance(e, np.ndarray) and e.ndim == 2 and e.dtype.kind == "f" for e in items]
+    empty = [e is None or np.size(e) == 0 for e in items]
+    if any(vec) and not all(v or z for v, z in zip(vec, empty)):
+        raise ValueError("examples: every user's examples must be labels, or every user's vectors")
+    offs = np.zeros(len(items) + 1, dtype=np.int64)
+    if any(vec):
+        dd = int(d) if d is not None else next(e.shape[1] for e, v in zip(items, vec) if v)
+        rows = [np.ascontiguousarray(e, dtype=np.float32) if v else np.zeros((0, dd), np.float32)
+                for e, v in zip(items, vec)]
+        if any(r.shape[1] != dd for r in rows):
+            raise ValueError(f"examples: vectors must have {dd} columns")
+        np.cumsum([r.shape[0] for r in rows], out=offs[1:])
+        return offs, None, np.ascontiguousarray(np.concatenate(rows, axis=0), dtype=np.float32)
+    lists = [np.asarray(e if e is not None else (), dtype=np.int64).ravel() for e in items]
+    if items:
+        np.cumsum([l.size for l in lists], out=offs[1:])
+    labels = np.concatenate(lists) if items and offs[-1] else np.zeros(0, dtype=np.int64)
+    return offs, np.ascontiguousarray(labels, dtype=np.int64), None
+
+
+def examples_stats(reset: bool = False):
+    """(users searched, rounds run, users searched again) of the example
+    searches of this process since the last reset."""
+    a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().vs_examples_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                             1 if reset else 0), "vs_examples_stats")
+    return a.value, b.value, c.value
 
 
 def gather_picks(D, I, pos, metric: int):
@@ -697,6 +743,73 @@ class IndexFlat(Index):
             self._h, grouping._h, ctypes.c_void_p(xq_ptr), int(n), int(k), None, None,
             ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags, ctypes.c_void_p(stream)),
             "vs_search_distinct")
+
+    def _examples_args(self, positive, negative):
+        poffs, plab, pvec = examples_csr(positive, None, self._d)
+        n = poffs.size - 1
+        noffs = nlab = nvec = None
+        if negative is not None:
+            noffs, nlab, nvec = examples_csr(negative, n, self._d)
+            if noffs[-1] == 0:
+                noffs = nlab = nvec = None
+        if noffs is not None and (pvec is None) != (nvec is None):
+            raise ValueError("positive and negative examples must take the same form")
+        return n, poffs, plab, pvec, noffs, nlab, nvec
+
+    def _examples_call(self, n, k, poffs, plab, pvec, noffs, nlab, nvec, eoffs, elabels,
+                       exclude_examples, D, I, E, flags, stream):
+        op = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        pp = lambda a: _ptr(a) if a is not None else None  # noqa: E731
+        if pvec is not None:
+            _lib.check(self._lib.vs_search_examples_x(
+                self._h, op(poffs), pp(pvec), op(noffs), pp(nvec), n, k, op(eoffs), pp(elabels),
+                D, I, E, flags, stream), "vs_search_examples_x")
+        else:
+            _lib.check(self._lib.vs_search_examples(
+                self._h, op(poffs), pp(plab), op(noffs), pp(nlab), n, k, op(eoffs), pp(elabels),
+                1 if exclude_examples else 0, D, I, E, flags, stream), "vs_search_examples")
+
+    def search_examples(self, positive, negative=None, k=10, *, exclude=None,
+                        exclude_examples: bool = True, return_example: bool = False):
+        """Recommendation from examples (Qdrant ``recommend`` with
+        ``strategy="best_score"``): for every user the k rows nearest to ANY of
+        its positive examples that no negative example is at least as near to,
+        in ascending (key, label) order.  ``positive`` / ``negative`` hold one
+        list of labels per user (stored rows), or one 2-D float array per user
+        (the vector form); every user needs a positive, ``negative`` may be
+        None.  ``exclude`` as in ``search``; ``exclude_examples`` also excludes
+        a user's own example labels (label form only: vectors name no rows).
+        Returns (D, I), D the score to the nearest positive; with
+        ``return_example`` also E (int32), that positive's position in the
+        user's list (-1 on padding).  Fewer than k such rows pad with label -1.
+        Exact; k <= 1024, at most 64 positives and 64 negatives per user."""
+        n, poffs, plab, pvec, noffs, nlab, nvec = self._examples_args(positive, negative)
+        k = int(k)
+        assert k > 0
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        E = np.empty((n, k), dtype=np.int32)
+        if n:
+            eoffs, elabels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+            self._examples_call(n, k, poffs, plab, pvec, noffs, nlab, nvec, eoffs, elabels,
+                                exclude_examples, D.ctypes.data, I.ctypes.data, E.ctypes.data, 0,
+                                None)
+        return (D, I, E) if return_example else (D, I)
+
+    def search_examples_device(self, positive, negative, k: int, D_ptr: int, I_ptr: int,
+                               E_ptr: int = 0, *, exclude=None, exclude_examples: bool = True,
+                               stream: int = 0) -> None:
+        """``search_examples`` with D, I (and E, 0: not wanted) on this index's
+        device, on ``stream`` (the call waits for the stream after every round;
+        a capturing stream is refused).  The example lists are host lists."""
+        n, poffs, plab, pvec, noffs, nlab, nvec = self._examples_args(positive, negative)
+        if n == 0:
+            return
+        eoffs, elabels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+        self._examples_call(n, int(k), poffs, plab, pvec, noffs, nlab, nvec, eoffs, elabels,
+                            exclude_examples, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+                            ctypes.c_void_p(E_ptr) if E_ptr else None, _lib.OUT_DEVICE,
+                            ctypes.c_void_p(stream))
 
     def mean_rows(self, profiles) -> np.ndarray:
         """The weighted means of stored rows, computed on the device: profile

@@ -899,6 +899,89 @@ class FAISS:
             out[p] = self._docs_of_row(scores[j], labels[j])
         return out
 
+    # -- example searches -------------------------------------------------------------------
+    def example_requests(self, liked, disliked=None, exclude=None, key: str = "book_id"):
+        """What ``index.search_examples`` takes for the users' liked and
+        disliked key values: (kept, positive, negative, lists, names).  kept =
+        the positions of the users with at least one liked key in the store;
+        positive[j] / negative[j] = the example labels of user kept[j], a key's
+        first row standing for it as in ``profile_requests`` (keys the store
+        does not hold drop out); lists[j] = every label of its liked, disliked
+        and excluded keys; names[j][i] = the key value of positive[j][i]."""
+        table = self._key_labels(key)
+        kept, positive, negative, lists, names = [], [], [], [], []
+        for u, values in enumerate(liked):
+            pos, neg, drop, name = [], [], [], []
+            for value in values:
+                found = table.get(value)
+                if found:
+                    pos.append(found[0])
+                    name.append(value)
+                    drop.extend(found)
+            if not pos:
+                continue
+            for value in (disliked[u] if disliked is not None else ()):
+                found = table.get(value)
+                if found:
+                    neg.append(found[0])
+                    drop.extend(found)
+            for value in (exclude[u] if exclude is not None else ()):
+                drop.extend(table.get(value, ()))
+            kept.append(u)
+            positive.append(pos)
+            negative.append(neg)
+            lists.append(drop)
+            names.append(name)
+        return kept, positive, negative, lists, names
+
+    def recommend_from_examples(self, liked, disliked=None, k: int = 4, *, exclude=None,
+                                key: str = "book_id", with_reason: bool = False):
+        """Recommendations from a reader's feedback itself instead of its mean
+        (``index.search_examples``; Qdrant's ``recommend`` with
+        ``strategy="best_score"``).  ``liked[i]`` / ``disliked[i]`` hold the
+        ``metadata[key]`` values user i rated up / down, ``exclude[i]`` further
+        values it must not get back.  A document is scored by its nearest liked
+        book and dropped when a disliked book is at least as near, so a
+        thumbs-down pushes away instead of pulling, and two tastes stay two
+        tastes.  No row of a liked, disliked or excluded key comes back.
+        Returns per user exactly min(k, such documents) ``(Document, score)``
+        pairs, best first; ``with_reason`` appends the liked key value that
+        decided each ("because you liked X").  A user none of whose liked keys
+        are in the store gets ``[]``.  Library-specific: LangChain's store has
+        no counterpart."""
+        liked = [list(v) for v in liked]
+        if disliked is not None:
+            disliked = [list(v) for v in disliked]
+            _len_check_if_sized(liked, disliked, "liked", "disliked")
+        if exclude is not None:
+            exclude = [list(v) for v in exclude]
+            _len_check_if_sized(liked, exclude, "liked", "exclude")
+        out: List[list] = [[] for _ in liked]
+        kept, positive, negative, lists, names = self.example_requests(liked, disliked, exclude,
+                                                                       key)
+        if not kept:
+            return out
+        if self._normalize_L2:  # the store normalises every vector it searches
+
+            def rows(labels):
+                vec = np.stack([self.index.reconstruct(int(l)) for l in labels]) if labels else \
+                    np.zeros((0, self.index.d), dtype=np.float32)
+                vec = np.ascontiguousarray(vec, dtype=np.float32)
+                vfaiss.normalize_L2(vec)
+                return vec
+
+            positive = [rows(p) for p in positive]
+            negative = [rows(n) for n in negative]
+        scores, labels, reason = self.index.search_examples(
+            positive, negative, k, exclude=lists, exclude_examples=False, return_example=True)
+        for j, u in enumerate(kept):
+            docs = self._docs_of_row(scores[j], labels[j])
+            if with_reason:
+                docs = [(doc, s, names[j][int(e)])
+                        for (doc, s), e in zip(docs, reason[j][labels[j] != -1])]
+            out[u] = docs
+        return out
+
     def _select_relevance_score_fn(self) -> Callable[[float], float]:
         if self.override_relevance_score_fn is not None:
             return self.override_relevance_score_fn

@@ -356,6 +356,91 @@ int vs_distinct_plan(int64_t k, int metric, int raw, int64_t live, int64_t* out,
  * (searched again at least once). */
 int vs_distinct_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int reset);
 
+/* ---- example searches ------------------------------------------------------
+ * Recommendation from examples (Qdrant recommend, strategy="best_score"): the
+ * rows nearest to ANY liked example that no disliked example is at least as
+ * near to.  The reference's reader path (src/recommendation_api/service.py:
+ * 423-554) averages the rated books into one query, where a thumbs-down only
+ * shrinks a weight (the disliked book still pulls the query towards itself)
+ * and two tastes average into a query near neither; vs_search_profiles keeps
+ * that mean bit for bit, these calls use the examples themselves.
+ *
+ * The index metric decides the key as everywhere: key = distance (L2) or
+ * -score (inner product), smaller is better.  key(e, r) of an example vector e
+ * and a stored row r is the rescoring's exact key: the fp64 sum of the
+ * products rounded once to fp32, then L2: max(0, (|e|^2 + |x|^2) - 2 e.x) with
+ * the staged |e|^2 and the stored |x|^2 — always this form, however many
+ * examples the call holds, so a user's answer does not depend on who else is
+ * in the call — or inner product: -e.x.  bf16 indexes round the example to
+ * bf16 first, as searches round their queries.
+ *
+ * For user u with positives P (at least one), negatives N (possibly none) and
+ * allowed rows A = the live rows minus u's exclusion list:
+ *   p(r) = min over e in P of key(e, r); the deciding example of r attains it,
+ *          among equal keys the lowest position in u's positive list;
+ *   n(r) = min over e in N of key(e, r), +inf without negatives;
+ *   r is favoured iff p(r) < n(r) — strictly: a row exactly as near to a
+ *   disliked example as to a liked one is not recommended.
+ * The result is the first k favoured rows of A in ascending (p, label) order
+ * (VS_RAW_ORDER's order; faiss's inner-product tie rule is not applied): this
+ * is Qdrant's best_score order cut where its score changes sign.  Fewer than k
+ * favoured rows pad with (+FLT_MAX | -FLT_MAX, -1).  D = p as a score (the
+ * distance, or the inner product), I = the label, E (n * k int32, may be NULL)
+ * = the deciding positive's position in the user's list, -1 on padding: the
+ * "because you liked X" of a recommender.
+ *
+ * vs_search_examples: the examples are stored rows by label, HOST CSRs as
+ * vs_mean_rows takes them (pos_offs / neg_offs: n + 1 int64 from 0; neg_offs
+ * may be NULL).  A label that is not a live label: VS_E_INVALID.  excl_offs /
+ * excl_labels as vs_search_excl (NULL: none); exclude_examples != 0 adds every
+ * example label of a user to that user's exclusion list.
+ * vs_search_examples_x: the same search with the examples as fp32 vectors,
+ * pos_x = pos_offs[n] * d and neg_x = neg_offs[n] * d floats in CSR order
+ * (VS_IN_DEVICE covers these two arrays).  Both forms converge on one device
+ * matrix of example rows — labels are gathered from the index (bf16 widened,
+ * as vs_reconstruct_n returns them), vectors are staged as queries are — so
+ * with stored rows given either way they return the same bits.
+ * flags: VS_OUT_DEVICE covers D, I and E.
+ *
+ * Exact (DESIGN.md "Example searches"): a round searches every positive of the
+ * users still unsettled in raw order for a window of w entries (the distinct
+ * searches' schedule: k + max(16, k / 2), four times longer every round, at
+ * last every live row), each positive with its user's exclusion list.  With F
+ * the smallest last entry of a user's windows, the rows at or before F in
+ * (p, label) order are known exactly; if k of them are favoured, or every
+ * window reached the end of the allowed rows, the user is settled, otherwise
+ * it alone is searched again.  The members of that set are rescored with the
+ * exact key before they are compared with the negatives and ordered (the same
+ * bits where the engine's key is the exact key already, as on fp32 indexes; a
+ * bf16 index's large batches accumulate in fp32, and there only the windows
+ * keep that engine's order).  A user with fewer than k favoured rows pays for
+ * the long windows: past 1,023 entries the paged engine answers, about w / 64
+ * passes over the rows per positive.  A round's scratch is 72 bytes per window
+ * entry, in batches of users of at most 1 GiB; a user whose own windows
+ * (positives x w) exceed that: VS_E_UNSUPPORTED when that round is reached.
+ *
+ * Checked before the index is read, in this order: the index, n >= 0, k > 0
+ * (VS_E_INVALID); k > 1024: VS_E_UNSUPPORTED; the offsets start at 0 and do
+ * not decrease; every user has at least one positive (VS_E_INVALID); more than
+ * 64 positives or 64 negatives of one user: VS_E_UNSUPPORTED (the reference
+ * caps a reader's history at 20 books, config.py:24); the exclusion offsets;
+ * the buffers.  n == 0 is success.  The call reads a 4-byte count after every
+ * round, so it waits for `stream`; a capturing stream: VS_E_UNSUPPORTED.
+ * Every user's examples lie in one engine chunk (65,536 positives). */
+int vs_search_examples(vs_index* idx, const int64_t* pos_offs, const int64_t* pos_labels,
+                       const int64_t* neg_offs, const int64_t* neg_labels, int64_t n, int64_t k,
+                       const int64_t* excl_offs, const int64_t* excl_labels, int exclude_examples,
+                       float* D, int64_t* I, int32_t* E, int flags, void* stream);
+int vs_search_examples_x(vs_index* idx, const int64_t* pos_offs, const float* pos_x,
+                         const int64_t* neg_offs, const float* neg_x, int64_t n, int64_t k,
+                         const int64_t* excl_offs, const int64_t* excl_labels, float* D, int64_t* I,
+                         int32_t* E, int flags, void* stream);
+/* Process-wide counters of the example searches since the last reset
+ * (reset != 0 clears them): users searched, rounds run (summed over the calls'
+ * chunks of users), and users whose first windows were too short (searched
+ * again at least once). */
+int vs_examples_stats(int64_t* users, int64_t* rounds, int64_t* requeried, int reset);
+
 /* ---- MMR searches ----------------------------------------------------------
  * LangChain's maximal-marginal-relevance searches
  * (FAISS.max_marginal_relevance_search*, as_retriever(search_type="mmr")):
