@@ -251,6 +251,8 @@ def mismatches(D, I, Dr, Ir, metric: int, xb, xq, rtol: float = 1e-5, strict: bo
     an exactly rescored key (key_window): D must be the fp32 rounding of the
     label's exact score, and a different label is a tie only when the two exact
     scores are within both windows — what the filter-and-verify engine proves.
+    Every tolerance test is "not within" (here, in mismatches_vec and in
+    selfjoin_mismatches), so a NaN D or a NaN exact score is a problem too.
     Returns a list of human-readable problems (empty = parity)."""
     xb = np.asarray(xb, dtype=np.float32)
     xq = np.asarray(xq, dtype=np.float32)
@@ -282,7 +284,7 @@ def mismatches(D, I, Dr, Ir, metric: int, xb, xq, rtol: float = 1e-5, strict: bo
                 tol = float(key_window(metric, s_got, nq2[q], nb2[ids[j]], xb.shape[1]))
             else:
                 tol = score_tolerance(metric, s_got, nq2[q], nb2[ids[j]]) * (rtol / 1e-5)
-            if abs(float(D[q, j]) - s_got) > tol:
+            if not abs(float(D[q, j]) - s_got) <= tol:  # a NaN is not within
                 bad.append((q, j, "score", float(D[q, j]), float(s_got), float(tol)))
             if ids[j] != Ir[q, j]:
                 s_ref = exact_scores(xb[Ir[q, j]:Ir[q, j] + 1], xq[q:q + 1], metric)[0, 0]
@@ -290,7 +292,7 @@ def mismatches(D, I, Dr, Ir, metric: int, xb, xq, rtol: float = 1e-5, strict: bo
                     tol2 = tol + float(key_window(metric, s_ref, nq2[q], nb2[Ir[q, j]], xb.shape[1]))
                 else:
                     tol2 = score_tolerance(metric, s_ref, nq2[q], nb2[Ir[q, j]]) * (rtol / 1e-5)
-                if abs(s_got - s_ref) > tol2:
+                if not abs(s_got - s_ref) <= tol2:
                     bad.append((q, j, "label", int(ids[j]), int(Ir[q, j]), s_got, s_ref, tol2))
     return bad
 
@@ -314,12 +316,12 @@ def selfjoin_mismatches(S, I, Sr, Ir, x, q_rows, strict: bool = False):
                 continue
             s_got = float(x64[q] @ x64[a]) / (nrm[q] * nrm[a])
             tol = float(key_window(0, s_got, 0, 0, d, cosine=True)) if strict else 1e-5
-            if abs(float(S[row, j]) - s_got) > tol:
+            if not abs(float(S[row, j]) - s_got) <= tol:  # a NaN is not within
                 bad.append((row, j, "sim", float(S[row, j]), s_got, tol))
             if a != b:
                 s_ref = float(x64[q] @ x64[b]) / (nrm[q] * nrm[b])
                 tol2 = tol + float(key_window(0, s_ref, 0, 0, d, cosine=True)) if strict else 1e-5
-                if abs(s_got - s_ref) > tol2 or a == int(q):
+                if not abs(s_got - s_ref) <= tol2 or a == int(q):
                     bad.append((row, j, "label", a, b, s_got, s_ref))
     return bad
 
@@ -403,14 +405,15 @@ def mismatches_vec(D, I, Dr, Ir, metric: int, xb, xq, rtol: float = 1e-5, qchunk
         valid = ids >= 0
         s_got = scores(ids, q0, q1)
         t_got = tol(s_got, ids, q0, q1)
-        off = valid & (np.abs(D[q0:q1].astype(np.float64) - s_got) > t_got)
+        # "not within", so that a NaN score is reported
+        off = valid & ~(np.abs(D[q0:q1].astype(np.float64) - s_got) <= t_got)
         for q, j in zip(*np.nonzero(off)):
             bad.append((q0 + int(q), int(j), "score", float(D[q0 + q, j]), float(s_got[q, j])))
         diff = valid & (ids != rids)
         if diff.any():
             s_ref = scores(rids, q0, q1)
             t_ref = tol(s_ref, rids, q0, q1)
-            lab = diff & (np.abs(s_got - s_ref) > t_got + t_ref)
+            lab = diff & ~(np.abs(s_got - s_ref) <= t_got + t_ref)
             for q, j in zip(*np.nonzero(lab)):
                 bad.append((q0 + int(q), int(j), "label", int(ids[q, j]), int(rids[q, j]),
                             float(s_got[q, j]), float(s_ref[q, j])))

@@ -293,3 +293,192 @@ def free_share_cosine(x, k, q_rows, skip=None):
     assert np.isfinite(s).all()
     w = flat.key_window(0, s, 0, 0, x64.shape[1], cosine=True)
     return _share(s, w, k)
+
+
+# ---- range searches and range self-joins on the row families ------------------------------------
+# The oracle side of tests/test_gpu_range_families.py; tests/test_row_families_host.py
+# admits every case from these functions alone.
+RANGE_QUANTILES = (0.001, 0.01, 0.2)  # the share of all pairs a search radius takes in
+RANGE_NQ = (100, 19)  # faiss's BLAS L2 key, and its sequential one (the first 19 queries)
+# Cosine quantiles of the join thresholds.  At 0.99 and 0.999 a query row of an
+# i.i.d. family has 60 +- 8 and 6 +- 3 hits of 6000, so no segment spans a
+# 128-row tile; 0.95 (about 300 hits a row) is there for that.
+JOIN_QUANTILES = (0.95, 0.99, 0.999)
+
+
+def family_half_mask(n, seed=1):
+    """The random half of n rows the selector cases select (bool mask)."""
+    return np.random.default_rng(seed).random(n) < 0.5
+
+
+def family_tombstones(xb, xq, count=50, seed=5):
+    """(rows to add, labels to remove, the rows then live): `count` random rows
+    of xb replaced by copies of the leading queries, each of which would be a
+    hit of its query."""
+    ids = np.random.default_rng(seed).choice(xb.shape[0], count, replace=False)
+    planted = np.array(xb)
+    planted[ids] = xq[np.arange(count) % xq.shape[0]]
+    return planted, ids, np.delete(planted, ids, axis=0)
+
+
+def plant_unselected(xb, xq, mask):
+    """Copies of the queries into unselected rows (three per query where they
+    fit): the unfiltered nearest rows then lie outside the selection."""
+    xb = np.array(xb)
+    out = np.nonzero(~mask)[0]
+    for j, r in enumerate(out[: 3 * xq.shape[0]]):
+        xb[r] = xq[j % xq.shape[0]]
+    return xb
+
+
+# A case in which the range search's bound decides (the quantile radii above
+# never do: at ld = 128 the bound is some hundred times the candidate GEMM's
+# actual error, so that no pair of theirs lies between the two).  BAND_ROWS
+# large rows (|x| ~ 1000), added after BAND_BASE small ones (|x| ~ 0.01), are
+# each built orthogonal to one of the first BAND_QUERIES queries (|q| ~ 10) up
+# to an inner product of BAND_RADIUS: their exact scores scatter about the
+# radius by the rounding of their coordinates (~3e-5), far more than the window
+# (U |s| ~ 1.5e-8) and less than the fp32 GEMM's error on such a row (~1e-4).
+# About half are hits, and the GEMM alone misclassifies a good part of them:
+# only a bound that knows the large rows' norm keeps them as candidates.
+BAND_BASE, BAND_ROWS, BAND_QUERIES, BAND_RADIUS = 2000, 1600, 8, np.float32(0.25)
+
+
+def bound_band_case(seed=7):
+    """(first add, second add, queries) of the band case, d = FAMILY_SHAPE[1]."""
+    d, nq = FAMILY_SHAPE[1], FAMILY_SHAPE[2]
+    rng = np.random.default_rng(seed)
+    base = np.ldexp(rng.standard_normal((BAND_BASE, d)), -10).astype(np.float32)
+    xq = rng.standard_normal((nq, d)).astype(np.float32)
+    q = xq[np.arange(BAND_ROWS) % BAND_QUERIES].astype(np.float64)
+    x = 100.0 * rng.standard_normal((BAND_ROWS, d))
+    qq = np.einsum("ij,ij->i", q, q)[:, None]
+    x += (float(BAND_RADIUS) - np.einsum("ij,ij->i", x, q)[:, None]) / qq * q
+    return base, x.astype(np.float32), xq
+
+
+def _norms2(x):
+    x64 = np.asarray(x, dtype=np.float64)
+    return np.einsum("ij,ij->i", x64, x64)
+
+
+def range_reference(xb, xq, metric):
+    """(s, w): the fp64 scores of every (query, row) pair and the window
+    flat.key_window an exactly computed, once-rounded key can sit in."""
+    s = flat.exact_scores(xb, xq, metric)
+    return s, flat.key_window(metric, s, _norms2(xq)[:, None], _norms2(xb)[None, :], xb.shape[1])
+
+
+def range_radius(s, metric, quantile):
+    """The radius that takes in the share `quantile` of the pairs of s."""
+    return np.float32(np.quantile(s, quantile if metric == flat.METRIC_L2 else 1.0 - quantile))
+
+
+def range_cap(hits):
+    """How many undecided pairs (|s - radius| <= w) a case of `hits` oracle hits
+    may have: a condition on the inputs, so that a case cannot pass because
+    everything was "undecided"."""
+    return max(2, int(hits) // 200)
+
+
+def join_reference(x, nq=None):
+    """(s, w): the fp64 cosines of the ordered pairs (q, r) of rows, q among
+    the first nq (default: all), NaN for a zero row, and their windows
+    flat.key_window(..., cosine=True)."""
+    x64 = np.asarray(x, dtype=np.float64)
+    n2 = np.einsum("ij,ij->i", x64, x64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = (x64[:nq] @ x64.T) / np.sqrt(np.outer(n2[:nq], n2))
+    return s, flat.key_window(0, s, 0, 0, x64.shape[1], cosine=True)
+
+
+def join_threshold(s, quantile, nq=FAMILY_JOIN_ROWS):
+    """The cosine at `quantile` of the pairs the first nq rows query (s of
+    join_reference): self pairs and zero rows (NaN already) left out."""
+    c = np.array(s[:nq], dtype=np.float64)
+    c[np.arange(nq), np.arange(nq)] = np.nan
+    return np.float32(np.nanquantile(c, quantile))
+
+
+def join_valid(nq, n, *, q0=0, exclude_self=True, upper=False):
+    """The pairs a self-join of rows q0 .. q0 + nq may return."""
+    rows = np.arange(n)[None, :]
+    qrow = np.arange(q0, q0 + nq)[:, None]
+    valid = np.ones((nq, n), dtype=bool)
+    if exclude_self:
+        valid &= rows != qrow
+    if upper:
+        valid &= rows > qrow
+    return valid
+
+
+def range_classes(s, w, radius, kind, valid=None):
+    """(hit, inside, outside) over the pairs of s for a threshold `radius`.
+    kind: flat.METRIC_L2 (a hit is s < radius), flat.METRIC_INNER_PRODUCT
+    (s > radius) or "cosine" (s >= radius).  hit is the fp64 oracle's own
+    answer; inside / outside are the pairs farther than their window from the
+    threshold, which every correct engine classifies the same way.  A NaN score
+    (a zero row's cosine) is outside; `valid` (bool, broadcastable) marks the
+    pairs that may be returned at all."""
+    r = float(radius)
+    with np.errstate(invalid="ignore"):
+        if kind == flat.METRIC_L2:
+            hit, inside, outside = s < r, s < r - w, ~(s <= r + w)
+        elif kind == flat.METRIC_INNER_PRODUCT:
+            hit, inside, outside = s > r, s > r + w, ~(s >= r - w)
+        elif kind == "cosine":
+            hit, inside, outside = s >= r, s >= r + w, ~(s >= r - w)
+        else:
+            raise ValueError(kind)
+    if valid is not None:
+        valid = np.broadcast_to(valid, s.shape)
+        hit, inside, outside = hit & valid, inside & valid, outside | ~valid
+    return hit, inside, outside
+
+
+def range_counts(s, w, radius, kind, valid=None):
+    """From the oracle alone: (hits, undecided, hits per query)."""
+    hit, inside, outside = range_classes(s, w, radius, kind, valid)
+    return int(hit.sum()), int((~(inside | outside)).sum()), hit.sum(axis=1)
+
+
+def range_contract(result, s, w, radius, kind, *, valid=None, base=0, timer=True, tag=""):
+    """The contract of a range search or range self-join result (lims, D, I)
+    against the oracle's (s, w) for its queries: lims well formed; labels
+    strictly ascending per query and inside the index; every pair inside the
+    threshold by more than its window present; none outside by more than its
+    window (or outside `valid`) returned; D within the window of the returned
+    label's fp64 score; at most range_cap(oracle hits) undecided pairs; and the
+    candidate pass was gemm_range.  Every comparison is written so that a NaN
+    fails it.  Returns (hits, undecided)."""
+    lims, D, I = result
+    nq, n = s.shape
+    if timer:
+        from vsearch import _lib
+
+        assert _lib.timer_kernel() == "gemm_range"
+    assert lims.dtype == np.uint64 and D.dtype == np.float32 and I.dtype == np.int64
+    assert lims.shape == (nq + 1,)
+    assert lims[0] == 0 and lims[-1] == len(D) == len(I)
+    li = lims.astype(np.int64)
+    assert (np.diff(li) >= 0).all()
+    q = np.repeat(np.arange(nq), np.diff(li))
+    r = I - base
+    assert ((r >= 0) & (r < n)).all(), "a label outside the index"
+    if len(I) > 1:  # strictly ascending between neighbours of one query's segment
+        same = q[1:] == q[:-1]
+        assert (np.diff(r)[same] > 0).all(), "labels not strictly ascending inside a query"
+    got = np.zeros((nq, n), dtype=bool)
+    got[q, r] = True
+    hit, inside, outside = range_classes(s, w, radius, kind, valid)
+    hits, undecided = int(hit.sum()), int((~(inside | outside)).sum())
+    print(f"range {tag}: hits {len(D)} oracle {hits} undecided {undecided} cap {range_cap(hits)}")
+    assert undecided <= range_cap(hits), (tag, undecided, hits)
+    assert got[inside].all(), (tag, "a pair inside the threshold is missing",
+                               int((inside & ~got).sum()))
+    assert not got[outside].any(), (tag, "a pair outside the threshold (or the selection) "
+                                    "was returned", int((outside & got).sum()))
+    err = np.abs(D.astype(np.float64) - s[q, r])
+    assert (err <= w[q, r]).all(), (tag, "D is not the exact key")
+    assert abs(len(D) - hits) <= undecided, (tag, len(D), hits, undecided)
+    return len(D), undecided

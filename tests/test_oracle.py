@@ -278,3 +278,84 @@ def test_simd_speed_standin_matches_scalar_labels(metric):
     Ds, Is = cfaiss.knn_seq_simd(xb, xq, 10, metric)
     np.testing.assert_array_equal(Is, I)
     np.testing.assert_allclose(Ds, D, rtol=1e-5, atol=1e-4)
+
+
+# ---- the parity checkers report NaN ----------------------------------------------------------------
+def _checker_case(metric, k=12, n=300, d=24, nq=9):
+    rng = np.random.default_rng(21)
+    xb = rng.standard_normal((n, d)).astype(np.float32)
+    xq = rng.standard_normal((nq, d)).astype(np.float32)
+    Dr, Ir = flat.knn_exact(xb, xq, k, metric)
+    return xb, xq, Dr, Ir
+
+
+@pytest.mark.parametrize("strict", [False, True])
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_mismatches_reports_a_nan_score(metric, strict):
+    """A correct result passes; one D[q, j] = NaN on a real label is reported
+    (abs(NaN - s) > tol is false: the test has to be "not within")."""
+    xb, xq, Dr, Ir = _checker_case(metric)
+    assert flat.mismatches(Dr, Ir, Dr, Ir, metric, xb, xq, strict=strict) == []
+    D = Dr.copy()
+    D[4, 7] = np.nan
+    bad = flat.mismatches(D, Ir, Dr, Ir, metric, xb, xq, strict=strict)
+    assert [b[:3] for b in bad] == [(4, 7, "score")]
+    # a NaN exact score (a non-finite stored row) is reported as well
+    xn = xb.copy()
+    xn[Ir[2, 3], 0] = np.nan
+    bad = flat.mismatches(Dr, Ir, Dr, Ir, metric, xn, xq, strict=strict)
+    assert (2, 3, "score") in [b[:3] for b in bad]
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_mismatches_vec_reports_a_nan_score(metric):
+    xb, xq, Dr, Ir = _checker_case(metric, k=70)
+    assert flat.mismatches_vec(Dr, Ir, Dr, Ir, metric, xb, xq) == []
+    D = Dr.copy()
+    D[4, 66] = np.nan
+    bad = flat.mismatches_vec(D, Ir, Dr, Ir, metric, xb, xq)
+    assert [b[:3] for b in bad] == [(4, 66, "score")]
+    # another label whose exact score is NaN is no tie
+    I = Ir.copy()
+    other = int(np.setdiff1d(np.arange(xb.shape[0]), Ir[1])[0])
+    I[1, 5] = other
+    xn = xb.copy()
+    xn[other, 0] = np.nan
+    bad = flat.mismatches_vec(Dr, I, Dr, Ir, metric, xn, xq)
+    assert {b[:3] for b in bad} >= {(1, 5, "score"), (1, 5, "label")}
+
+
+def test_mismatch_checkers_keep_exact_equality_on_padding():
+    """k > ntotal: padding slots must hold (neutral, -1) exactly, NaN included."""
+    for metric in (L2, IP):
+        xb, xq, Dr, Ir = _checker_case(metric, k=14, n=10)
+        assert (Ir[:, 10:] == -1).all()
+        assert flat.mismatches(Dr, Ir, Dr, Ir, metric, xb, xq) == []
+        assert flat.mismatches_vec(Dr, Ir, Dr, Ir, metric, xb, xq) == []
+        D = Dr.copy()
+        D[3, 12] = np.nan
+        assert [b[:3] for b in flat.mismatches(D, Ir, Dr, Ir, metric, xb, xq)] == [
+            (3, 12, "padding score")]
+        assert flat.mismatches_vec(D, Ir, Dr, Ir, metric, xb, xq) == [("padding score",)]
+
+
+@pytest.mark.parametrize("strict", [False, True])
+def test_selfjoin_mismatches_reports_a_nan_similarity(strict):
+    rng = np.random.default_rng(22)
+    x = rng.standard_normal((200, 24)).astype(np.float32)
+    q_rows = np.arange(40)
+    Sr, Ir = flat.pgvector_cosine_topk(x, 8, q_rows=q_rows)
+    assert flat.selfjoin_mismatches(Sr, Ir, Sr, Ir, x, q_rows, strict=strict) == []
+    S = Sr.copy()
+    S[11, 2] = np.nan
+    bad = flat.selfjoin_mismatches(S, Ir, Sr, Ir, x, q_rows, strict=strict)
+    assert [b[:3] for b in bad] == [(11, 2, "sim")]
+    # a label whose exact similarity is NaN (a zero row) is no tie of the oracle's
+    I = Ir.copy()
+    zero = int(np.setdiff1d(np.arange(40, 200), Ir[5])[0])
+    I[5, 1] = zero
+    xz = x.copy()
+    xz[zero] = 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        bad = flat.selfjoin_mismatches(Sr, I, Sr, Ir, xz, q_rows, strict=strict)
+    assert {b[:3] for b in bad} >= {(5, 1, "sim"), (5, 1, "label")}
