@@ -132,6 +132,33 @@ struct vs_grouping {
   int32_t* dgroup = nullptr;  // [nrows]
 };
 
+// The attributes of one index (vs_attrs_create): up to four float columns and
+// one 64-bit tag word per label, on the device by label and by row in place
+// (one array without tombstones), valid while the index's generation is the
+// one they were built at.
+struct vs_attrs {
+  vs_index* idx = nullptr;
+  int device = 0;
+  uint64_t gen = 0;
+  int64_t n = 0;      // labels given = the live rows at creation
+  int64_t nrows = 0;  // rows in place the by-row arrays cover
+  int ncol = 0;
+  float* lcols = nullptr;               // [ncol][n]
+  unsigned long long* ltags = nullptr;  // [n], null: all 0
+  float* rcols = nullptr;               // [ncol][nrows]
+  unsigned long long* rtags = nullptr;  // [nrows], null: all 0
+  uint8_t* rlive = nullptr;             // [nrows], null: no tombstones
+  vs::WhereAttrs by_row() const {
+    vs::WhereAttrs a;
+    a.cols = rcols;
+    a.tags = rtags;
+    a.live = rlive;
+    a.ncol = ncol;
+    a.stride = nrows;
+    return a;
+  }
+};
+
 // Route (b) of vs_search_sel serves selections that leave at most this many
 // live rows out (a fixed condition of the route, not a tuned threshold).
 constexpr int64_t kSelMaxExcluded = 256;
@@ -578,6 +605,42 @@ inline int64_t distinct_window(int64_t need, int round, int64_t live) {
   int64_t w = need + std::max<int64_t>(16, need / 2);
   for (int r = 0; r < round && w < live; ++r) w *= 4;
   return std::min(w, live);
+}
+
+// ---- where searches (vs_api_where.hip) -----------------------------------------
+// The longest window of route A: the staged engine's candidate limit.  Past
+// it the paged engine would answer in w / 64 passes; the predicated scan
+// answers in one.
+constexpr int64_t kWhereMaxWindow = 1023;
+// Calls of at most kWhereCountMaxQ queries count their predicates' rows first
+// and scan at once the queries whose passing fraction is below the crossover.
+// Measured (DESIGN.md section 7 "Where searches", 10M x 1536 fp32, k = 10): the
+// scan wins at p = 0.03 and below at batch 1 (7.1-7.2 ms against 11.9-21.8)
+// and from p = 0.01 at batch 8 (13.5 against 26-29; p = 0.03 is a tie), the
+// windows win at p = 0.1 at batch 8 (12.3-15.8 against 34.6-38.3) and for L2
+// at batch 1.  The byte ratio of the int8 plane to the fp32 row (1/4), the
+// value this started from, sent p = 0.1 at batch 8 to a scan 2.2-3.1x slower.
+constexpr int kWhereCountMaxQ = 32;
+constexpr double kWhereCrossover = 0.05;
+// The windows of a where search (distinct_window's, while at most
+// kWhereMaxWindow or every live row) into out[0 .. nmax); returns how many the
+// whole schedule has, *scan = what they leave unsettled goes to the scan
+// (false: the last window is every live row).
+inline int where_windows(int64_t need, int64_t live, int64_t* out, int nmax, bool* scan) {
+  int n = 0;
+  *scan = false;
+  if (live <= 0) return 0;
+  for (int r = 0;; ++r) {
+    const int64_t w = distinct_window(need, r, live);
+    if (w < live && w > kWhereMaxWindow) {
+      *scan = true;
+      break;
+    }
+    if (n < nmax) out[n] = w;
+    ++n;
+    if (w >= live) break;
+  }
+  return n;
 }
 
 }  // namespace host

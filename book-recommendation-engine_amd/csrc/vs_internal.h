@@ -739,4 +739,92 @@ struct ExamplesCollapse {
 };
 hipError_t launch_examples_collapse(const ExamplesCollapse& c, hipStream_t st);
 
+// Where searches (vs_where.hip; vs_api_where.hip vs_attrs_* / vs_search_where).
+constexpr int kWhereMaxCols = 4;
+// One query's predicate: column c < ncol is tested iff bit c of cmask is set
+// and passes iff lo[c] <= v && v <= hi[c] (a NaN value fails); the tag tests
+// are any_of == 0 || (tags & any_of), (tags & all_of) == all_of and
+// (tags & none_of) == 0.  on == 0: a padding slot, nothing passes.
+struct WherePred {
+  float lo[kWhereMaxCols];
+  float hi[kWhereMaxCols];
+  unsigned long long any_of, all_of, none_of;
+  unsigned cmask;
+  unsigned on;
+};
+static_assert(sizeof(WherePred) == 64, "sixteen dwords");
+// The attributes of the rows in place (device): column c of row r at
+// cols[c * stride + r]; tags null: every row's tags are 0; live null: every
+// row is live, else live[r] == 0 marks a tombstoned row (it passes nothing).
+struct WhereAttrs {
+  const float* cols = nullptr;
+  const unsigned long long* tags = nullptr;
+  const uint8_t* live = nullptr;
+  int ncol = 0;
+  int64_t stride = 0;
+};
+// The by-row arrays of a tombstoned index from the by-label ones (nlab labels,
+// column stride nlab; by row: stride ntotal): row r holds the attributes of
+// label r - (dead rows below r); a dead row NaN columns, tags 0, live 0.
+hipError_t launch_attrs_spread(const float* lcols, const unsigned long long* ltags, int64_t nlab,
+                               int ncol, const int64_t* dead, int64_t ndead, int64_t ntotal,
+                               float* rcols, unsigned long long* rtags, uint8_t* live,
+                               hipStream_t st);
+// out[q] = the live rows of [0, nrows) that pass preds[q] (out is zeroed first).
+hipError_t launch_attrs_count(const WhereAttrs& at, int64_t nrows, const WherePred* preds, int nq,
+                              unsigned long long* out, hipStream_t st);
+// Slot s of Din / Iin ([ns][w] raw entries: ascending (key, label), labels =
+// row + id_base, -1 after the end) is query q = qmap ? qmap[s] : s; its entries
+// whose row passes preds[q], in order, at most `need` of them, are the first
+// entries of row s of Dout / Iout ([ns][kout], padded with the empty result of
+// `mode`); unsettled[q] = 1 when the window was too short (fewer than `need`
+// kept, no -1 entry seen, and not w_is_all), else 0.
+hipError_t launch_where_drop(int mode, const float* Din, const int64_t* Iin, int ns, int w,
+                             const WhereAttrs& at, const WherePred* preds, const int* qmap,
+                             int64_t id_base, int need, bool w_is_all, float* Dout, int64_t* Iout,
+                             int kout, int* unsettled, hipStream_t st);
+// The predicated scan's kernels: launch_gemm_topk / launch_gemv_topk at KP = 64
+// with floors, where a row enters query q's list only if it passes preds[q]
+// and is not in xrows[xoffs[q] .. xoffs[q + 1]) (ascending rows in place; both
+// null: no exclusions).  preds / xoffs / the floors are indexed like qaux (by
+// the query's row in Q: qlist[slot] for the GEMM, 0 .. nq - 1 for the GEMV,
+// whose preds hold kGemvMaxQ entries, `on` clear past nq).
+struct GemmWhereArgs {
+  const void* X = nullptr;
+  const float* xaux = nullptr;
+  const void* Q = nullptr;
+  const float* qaux = nullptr;
+  int64_t ld = 0;
+  int esize = 4, ntotal = 0, nq_pad = 0, nsplit = 0;
+  const int* qlist = nullptr;   // slot s is query row qlist[s], s < *qcount
+  const int* qcount = nullptr;
+  const float* fkey = nullptr;
+  const int* fid = nullptr;
+  WhereAttrs at;
+  const WherePred* preds = nullptr;
+  const int64_t* xoffs = nullptr;
+  const int64_t* xrows = nullptr;
+};
+hipError_t launch_gemm_topk_where(int mode, const GemmWhereArgs& a, Partials part,
+                                  hipStream_t st);
+struct GemvWhereArgs {
+  const void* X = nullptr;
+  const float* Q = nullptr;
+  int64_t ld = 0;
+  int esize = 4, ntotal = 0, nblocks = 0;
+  const float* fkey = nullptr;
+  const int* fid = nullptr;
+  const int* run = nullptr;  // optional: every block exits when *run == 0
+  WhereAttrs at;
+  const WherePred* preds = nullptr;
+  const int64_t* xoffs = nullptr;
+  const int64_t* xrows = nullptr;
+  unsigned long long* streamed = nullptr;  // optional: += the rows the launch loaded
+};
+// Modes IP and L2D, nq <= kGemvMaxQ, one list per query per block (part.P ==
+// nblocks).  A 4-row step none of whose rows passes any query's predicate is
+// not loaded.
+hipError_t launch_gemv_topk_where(int mode, int nq, const GemvWhereArgs& a, Partials part,
+                                  hipStream_t st);
+
 }  // namespace vs

@@ -22,6 +22,7 @@ DTYPE_BF16 = 1
 IN_DEVICE = 1
 OUT_DEVICE = 2
 RAW_ORDER = 4
+WHERE_SCAN = 8
 MAX_K = 64
 ENGINE_AUTO = 0
 ENGINE_FP32_MFMA = 1
@@ -76,6 +77,13 @@ SIGNATURES = {
                                     _vp]),
     "vs_distinct_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _vp, _c_int]),
     "vs_distinct_stats": (_c_int, [_i64p, _i64p, _i64p, _c_int]),
+    "vs_attrs_create": (_c_int, [_vp, _c_int, _vp, _vp, _c_i64, _vp, ctypes.POINTER(_vp)]),
+    "vs_attrs_destroy": (_c_int, [_vp]),
+    "vs_attrs_count": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+    "vs_search_where": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _c_int, _vp]),
+    "vs_where_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _vp, _c_int]),
+    "vs_where_stats": (_c_int, [_i64p, _i64p, _i64p, _i64p, _i64p, _c_int]),
     "vs_search_examples": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
                                     _vp, _vp, _c_int, _vp]),
     "vs_search_examples_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp,

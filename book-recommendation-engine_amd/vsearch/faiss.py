@@ -456,6 +456,137 @@ def distinct_stats(reset: bool = False):
     return a.value, b.value, c.value
 
 
+MAX_WHERE_COLUMNS = 4
+
+
+def where_arrays(where, ncol: int, nq: int):
+    """The arrays of ``vs_search_where`` for ``nq`` queries over ``ncol``
+    numeric columns: ``(lo, hi, masks)`` = float32 (nq, ncol), float32
+    (nq, ncol), uint64 (nq, 3) with any_of, all_of, none_of.
+
+    ``where`` is one predicate for every query or a sequence of ``nq`` of them.
+    A predicate is ``None`` (no test) or a mapping with the optional keys
+    ``"lo"`` / ``"hi"`` (``ncol`` values, ``None`` = unbounded: the closed
+    range a column must lie in) and ``"any_of"`` / ``"all_of"`` / ``"none_of"``
+    (tag bit masks).  An ``(lo, hi, masks)`` triple of arrays of those shapes
+    passes through."""
+    ncol, nq = int(ncol), int(nq)
+    if isinstance(where, tuple) and len(where) == 3 and not isinstance(where[0], (dict, type(None))):
+        lo = np.ascontiguousarray(where[0], dtype=np.float32).reshape(nq, ncol)
+        hi = np.ascontiguousarray(where[1], dtype=np.float32).reshape(nq, ncol)
+        masks = np.ascontiguousarray(where[2], dtype=np.uint64).reshape(nq, 3)
+    else:
+        preds = [where] * nq if where is None or isinstance(where, dict) else list(where)
+        if len(preds) != nq:
+            raise ValueError(f"where: {len(preds)} predicates for {nq} queries")
+        lo = np.full((nq, ncol), -np.inf, dtype=np.float32)
+        hi = np.full((nq, ncol), np.inf, dtype=np.float32)
+        masks = np.zeros((nq, 3), dtype=np.uint64)
+        for q, p in enumerate(preds):
+            if p is None:
+                continue
+            unknown = set(p) - {"lo", "hi", "any_of", "all_of", "none_of"}
+            if unknown:
+                raise ValueError(f"where: unknown keys {sorted(unknown)}")
+            for key, arr, dflt in (("lo", lo, -np.inf), ("hi", hi, np.inf)):
+                vals = p.get(key)
+                if vals is None:
+                    continue
+                vals = list(vals)
+                if len(vals) != ncol:
+                    raise ValueError(f"where: {key} holds {len(vals)} values for {ncol} columns")
+                arr[q] = [dflt if v is None else v for v in vals]
+            for j, key in enumerate(("any_of", "all_of", "none_of")):
+                masks[q, j] = np.uint64(int(p.get(key, 0)) & (2**64 - 1))
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("where: a NaN bound")
+    return lo, hi, masks
+
+
+class Attributes:
+    """Device handle of the attributes of one index (``IndexFlat.attributes``):
+    up to four float32 columns and one 64-bit tag word per label.  Reusable
+    across ``search_where`` calls until the index changes (add, remove_ids,
+    reset), after which searching with it raises RuntimeError ("stale
+    attributes"); ``index.update`` leaves it valid."""
+
+    def __init__(self, index: "IndexFlat", columns, tags=None):
+        self._lib = index._lib
+        self._h = ctypes.c_void_p()
+        self.index = index
+        cols = np.zeros((0, 0), dtype=np.float32) if columns is None else \
+            np.ascontiguousarray(columns, dtype=np.float32)
+        if cols.ndim == 1:
+            cols = cols.reshape(1, -1) if cols.size else cols.reshape(0, 0)
+        if cols.ndim != 2 or cols.shape[0] > MAX_WHERE_COLUMNS:
+            raise ValueError(f"attributes: at most {MAX_WHERE_COLUMNS} columns of one value per label")
+        self.ncol = int(cols.shape[0])
+        if tags is not None:
+            tags = np.ascontiguousarray(tags, dtype=np.uint64).reshape(-1)
+        n = int(cols.shape[1]) if self.ncol else (int(tags.size) if tags is not None
+                                                  else index.ntotal)
+        if tags is not None and tags.size != n:
+            raise ValueError(f"attributes: {tags.size} tags for {n} labels")
+        self.n = n
+        _lib.check(self._lib.vs_attrs_create(index._h, self.ncol, _ptr(cols),
+                                             _ptr(tags) if tags is not None else None, n, None,
+                                             ctypes.byref(self._h)), "vs_attrs_create")
+
+    def count(self, where, nq: int | None = None) -> np.ndarray:
+        """The live rows that pass each predicate (int64; ``where`` as in
+        ``where_arrays``: one predicate, or a sequence of them)."""
+        if nq is None:
+            nq = 1 if where is None or isinstance(where, dict) else \
+                (np.asarray(where[2]).reshape(-1, 3).shape[0] if isinstance(where, tuple)
+                 else len(where))
+        lo, hi, masks = where_arrays(where, self.ncol, nq)
+        out = np.zeros(nq, dtype=np.int64)
+        _lib.check(self._lib.vs_attrs_count(self._h, _ptr(lo), _ptr(hi), _ptr(masks), nq,
+                                            _ptr(out), None), "vs_attrs_count")
+        return out
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h is None or not h.value:
+            return
+        try:
+            self._lib.vs_attrs_destroy(h)
+        except Exception:  # interpreter shutdown: the library may be gone
+            pass
+        h.value = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def where_plan(k: int, metric: int, raw: bool, live: int):
+    """The windows of a where search for k over ``live`` rows, round by round,
+    then 0 when what they leave goes to the scan (vs_where_plan; touches no
+    device)."""
+    lib = _lib.load()
+    out = np.zeros(64, dtype=np.int64)
+    n = lib.vs_where_plan(int(k), int(metric), 1 if raw else 0, int(live), out.ctypes.data,
+                          out.size)
+    _lib.check(min(n, 0), "vs_where_plan")
+    return [int(v) for v in out[:n]]
+
+
+def where_stats(reset: bool = False):
+    """(queries searched, window rounds run, queries searched again, queries
+    answered by the scan, rows the scan's streaming kernel loaded) of the
+    where searches of this process since the last reset."""
+    v = [ctypes.c_int64(0) for _ in range(5)]
+    _lib.check(_lib.load().vs_where_stats(*[ctypes.byref(x) for x in v], 1 if reset else 0),
+               "vs_where_stats")
+    return tuple(x.value for x in v)
+
+
 class Index:
     """Common base (faiss.Index)."""
 
@@ -743,6 +874,55 @@ class IndexFlat(Index):
             self._h, grouping._h, ctypes.c_void_p(xq_ptr), int(n), int(k), None, None,
             ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags, ctypes.c_void_p(stream)),
             "vs_search_distinct")
+
+    def attributes(self, columns, tags=None) -> Attributes:
+        """The device handle of per-label attributes: ``columns`` holds up to
+        four sequences of ``ntotal`` numbers (NaN: unknown; ``None``: no
+        columns), ``tags`` one 64-bit word per label (``None``: all 0)."""
+        if isinstance(columns, Attributes):
+            return columns
+        return Attributes(self, columns, tags)
+
+    def search_where(self, x, k, attrs: Attributes, where, *, exclude=None, raw: bool = False,
+                     scan: bool = False):
+        """What ``search`` would return on an index that held only the rows
+        that pass the query's predicate: ``where`` is one predicate for every
+        query or one per query (``where_arrays``), over the columns and tags of
+        ``attrs`` (``index.attributes``); ``exclude`` and ``raw`` as in
+        ``search``.  Fewer than k matches pad with label -1.  ``scan=True``
+        skips the windows and answers every query with the predicated scan."""
+        x = _as_f32_rows(x)
+        n, d = x.shape
+        assert d == self._d
+        k = int(k)
+        assert k > 0
+        if attrs.index is not self:
+            raise ValueError("the Attributes belong to another index")
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        lo, hi, masks = where_arrays(where, attrs.ncol, n)
+        offs, labels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+        flags = (_lib.RAW_ORDER if raw else 0) | (_lib.WHERE_SCAN if scan else 0)
+        _lib.check(self._lib.vs_search_where(
+            self._h, attrs._h, _ptr(x), n, k, _ptr(lo), _ptr(hi), _ptr(masks),
+            offs.ctypes.data if offs is not None else None,
+            _ptr(labels) if labels is not None else None, _ptr(D), _ptr(I), flags, None),
+            "vs_search_where")
+        return D, I
+
+    def search_where_device(self, xq_ptr: int, n: int, k: int, attrs: Attributes, where,
+                            D_ptr: int, I_ptr: int, stream: int = 0, raw: bool = False,
+                            scan: bool = False) -> None:
+        """``search_where`` with the queries and the results on this index's
+        device, on `stream` (the call waits for the stream after every round; a
+        capturing stream is refused).  The predicates stay host arrays."""
+        lo, hi, masks = where_arrays(where, attrs.ncol, n)
+        flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE | (_lib.RAW_ORDER if raw else 0)
+                 | (_lib.WHERE_SCAN if scan else 0))
+        _lib.check(self._lib.vs_search_where(
+            self._h, attrs._h, ctypes.c_void_p(xq_ptr), int(n), int(k), _ptr(lo), _ptr(hi),
+            _ptr(masks), None, None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags,
+            ctypes.c_void_p(stream)), "vs_search_where")
 
     def _examples_args(self, positive, negative):
         poffs, plab, pvec = examples_csr(positive, None, self._d)

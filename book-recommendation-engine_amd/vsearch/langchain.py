@@ -33,6 +33,10 @@ types and error behaviour:
   embeddings, search, drop the books already read) for many students in one
   device call; ``similarity_search_with_score_by_vector(..., exclude_ids=)``
   for one query.
+* ``where=`` (library-specific) — a metadata predicate per query run inside
+  the search on the device (``index.search_where``), where the reference
+  filters an over-fetch on the host (candidate_builder.py:187-203,
+  service.py:529-542, mcp_book_server.py:615-682).
 """
 
 from __future__ import annotations
@@ -192,6 +196,123 @@ def _create_filter_func(filter: Any) -> Callable[[Dict[str, Any]], bool]:
     return build(filter)
 
 
+# ``where=``: the predicate grammar of the device-side filtered search
+# (``index.search_where``).  A predicate is a dict over metadata fields; a
+# numeric field takes $gte $lte $gt $lt $eq (closed float32 ranges: a strict
+# bound becomes np.nextafter in float32), a categorical or list-valued field
+# $in $all $nin $neq $eq (tag bits); a bare value is $eq.
+_WHERE_NUM_OPS = ("$gte", "$lte", "$gt", "$lt", "$eq")
+_WHERE_TAG_OPS = ("$in", "$all", "$nin", "$neq", "$eq")
+_WHERE_ROUTE = " (filter= with exact_filter=True is the general route)"
+WHERE_MAX_PAIRS = 64
+
+
+def _is_number(v: Any) -> bool:
+    return isinstance(v, (int, float, np.integer, np.floating)) and \
+        not isinstance(v, (bool, np.bool_))
+
+
+def _where_conditions(pred: Any) -> List[Tuple[str, str, Any]]:
+    """[(field, operator, value)] of one predicate."""
+    if not isinstance(pred, dict):
+        raise ValueError("where: a predicate is a dict over metadata fields" + _WHERE_ROUTE)
+    out = []
+    for field, cond in pred.items():
+        if isinstance(field, str) and field.startswith("$"):
+            raise ValueError(f"where: operator {field} is not supported" + _WHERE_ROUTE)
+        if isinstance(cond, dict):
+            for op, value in cond.items():
+                out.append((field, op, value))
+        else:
+            out.append((field, "$eq", cond))
+    return out
+
+
+def _where_values(op: str, value: Any) -> List[Any]:
+    if op in ("$in", "$all", "$nin"):
+        if not isinstance(value, (list, tuple, set, frozenset)):
+            raise ValueError(f"where: {op} takes a list of values")
+        return list(value)
+    return [value]
+
+
+def where_layout(preds, is_numeric: Callable[[str], bool]):
+    """What the predicates need of an attribute handle: (the numeric fields,
+    the (field, value) pairs of the tag vocabulary), both sorted.  More than 4
+    numeric fields, more than 64 pairs or an operator outside the grammar is a
+    ValueError."""
+    nums: List[str] = []
+    pairs: List[Tuple[str, Any]] = []
+    for pred in preds:
+        if pred is None:
+            continue
+        for field, op, value in _where_conditions(pred):
+            if is_numeric(field):
+                if op not in _WHERE_NUM_OPS:
+                    raise ValueError(f"where: operator {op} on the numeric field {field!r} is "
+                                     "not supported" + _WHERE_ROUTE)
+                if not _is_number(value) or math.isnan(float(value)):
+                    raise ValueError(f"where: {field!r} {op} takes a number")
+                if field not in nums:
+                    nums.append(field)
+            else:
+                if op not in _WHERE_TAG_OPS:
+                    raise ValueError(f"where: operator {op} on the field {field!r} is not "
+                                     "supported" + _WHERE_ROUTE)
+                for v in _where_values(op, value):
+                    if (field, v) not in pairs:
+                        pairs.append((field, v))
+    if len(nums) > vfaiss.MAX_WHERE_COLUMNS:
+        raise ValueError(f"where: more than {vfaiss.MAX_WHERE_COLUMNS} numeric fields"
+                         + _WHERE_ROUTE)
+    if len(pairs) > WHERE_MAX_PAIRS:
+        raise ValueError(f"where: more than {WHERE_MAX_PAIRS} (field, value) pairs" + _WHERE_ROUTE)
+    return tuple(sorted(nums)), tuple(sorted(pairs, key=repr))
+
+
+def where_predicate(pred, nums: Sequence[str], pairs: Sequence[Tuple[str, Any]]) -> Optional[dict]:
+    """One predicate of the grammar as ``index.search_where`` takes it
+    (``vfaiss.where_arrays``), over the columns ``nums`` and the tag bits
+    ``pairs`` of ``where_layout``.  Conditions on one field intersect.  $in of
+    several values sets any_of, which holds one such condition per predicate;
+    $eq and $in of one value test the value's bit through all_of (the same
+    test), so any number of fields may carry them."""
+    if pred is None:
+        return None
+    lo = [-np.inf] * len(nums)
+    hi = [np.inf] * len(nums)
+    masks = {"any_of": 0, "all_of": 0, "none_of": 0}
+    f32 = np.float32
+    for field, op, value in _where_conditions(pred):
+        if field in nums:
+            c = nums.index(field)
+            v = f32(value)
+            if op == "$gt":
+                v = np.nextafter(v, f32(np.inf))
+            elif op == "$lt":
+                v = np.nextafter(v, f32(-np.inf))
+            if op in ("$gte", "$gt", "$eq"):
+                lo[c] = max(lo[c], float(v))
+            if op in ("$lte", "$lt", "$eq"):
+                hi[c] = min(hi[c], float(v))
+            continue
+        bits = 0
+        for v in _where_values(op, value):
+            bits |= 1 << pairs.index((field, v))
+        if op in ("$nin", "$neq"):
+            masks["none_of"] |= bits
+        elif op == "$all" or bin(bits).count("1") == 1:
+            masks["all_of"] |= bits
+        elif bits == 0:  # $in []: nothing matches (a bit must be set and none may be)
+            masks["any_of"] = masks["none_of"] = 2**64 - 1
+        elif masks["any_of"]:
+            raise ValueError("where: $in of several values on more than one field"
+                             + _WHERE_ROUTE)
+        else:
+            masks["any_of"] = bits
+    return dict(lo=lo, hi=hi, **masks)
+
+
 class FAISS:
     """Vector store over a vsearch flat index (LangChain ``FAISS`` API)."""
 
@@ -214,6 +335,9 @@ class FAISS:
         self._sel_cache: Dict[str, Any] = {}
         # distinct= groupings by metadata field; dropped whenever _sel_cache is
         self._grp_cache: Dict[str, Any] = {}
+        # where= attribute handles by (numeric fields, tag vocabulary), and the
+        # kind of every field a predicate named; dropped whenever _sel_cache is
+        self._attr_cache: Dict[Any, Any] = {}
         # (field, metadata[field] -> labels), built once per store generation
         # (the labels move with every delete): dropped with _sel_cache
         self._keylabels: Optional[Tuple[str, Dict[Any, List[int]]]] = None
@@ -260,6 +384,7 @@ class FAISS:
             vfaiss.normalize_L2(vector)
         self._sel_cache.clear()
         self._grp_cache.clear()
+        self._attr_cache.clear()
         self._keylabels = None
         self.index.add(vector)
         self.docstore.add({id_: doc for id_, doc in zip(ids, documents)})
@@ -399,6 +524,7 @@ class FAISS:
         if changed:  # a filter or a grouping may read the fields that changed
             self._sel_cache.clear()
             self._grp_cache.clear()
+            self._attr_cache.clear()
             self._keylabels = None
         if extra:  # after the update: a delete renumbers the labels
             self.delete(extra)
@@ -431,6 +557,7 @@ class FAISS:
         index_to_delete = {reversed_index[id_] for id_ in ids}
         self._sel_cache.clear()
         self._grp_cache.clear()
+        self._attr_cache.clear()
         self._keylabels = None
         self.index.remove_ids(np.fromiter(index_to_delete, dtype=np.int64))
         if self._keymap_field is not None:
@@ -458,6 +585,7 @@ class FAISS:
         index_offset = len(self.index_to_docstore_id)
         self._sel_cache.clear()
         self._grp_cache.clear()
+        self._attr_cache.clear()
         self._keylabels = None
         if target.index.ntotal:
             self.index.add(target.index.reconstruct_n(0, target.index.ntotal))
@@ -564,6 +692,58 @@ class FAISS:
             grp = self._grp_cache[field] = self.index.grouping(keys)
         return grp
 
+    def _metadata_column(self, field: str) -> List[Any]:
+        out = []
+        for i in range(len(self.index_to_docstore_id)):
+            doc = self.docstore.search(self.index_to_docstore_id[i])
+            out.append(doc.metadata.get(field) if isinstance(doc, Document) else None)
+        return out
+
+    def _where_is_numeric(self, field: str) -> bool:
+        """A field is numeric when every document that has it holds a number."""
+        key = ("kind", field)
+        if key not in self._attr_cache:
+            vals = [v for v in self._metadata_column(field) if v is not None]
+            self._attr_cache[key] = bool(vals) and all(_is_number(v) for v in vals)
+        return self._attr_cache[key]
+
+    def _where_attributes(self, nums, pairs):
+        """The index's attribute handle over the numeric fields `nums` (NaN
+        where a document has no value) and one tag bit per (field, value) pair
+        of `pairs` (set where metadata[field] equals the value or, list-valued,
+        holds it).  Built once per layout and kept until the store changes."""
+        key = (nums, tuple(repr(p) for p in pairs))
+        attrs = self._attr_cache.get(key)
+        if attrs is None:
+            n = len(self.index_to_docstore_id)
+            cols = np.full((len(nums), n), np.nan, dtype=np.float32)
+            for c, field in enumerate(nums):
+                for i, v in enumerate(self._metadata_column(field)):
+                    if v is not None:
+                        cols[c, i] = v
+            tags = np.zeros(n, dtype=np.uint64)
+            for field in sorted({f for f, _ in pairs}):
+                bit = {v: np.uint64(1 << j) for j, (f, v) in enumerate(pairs) if f == field}
+                for i, v in enumerate(self._metadata_column(field)):
+                    for x in (v if isinstance(v, (list, tuple, set, frozenset)) else (v,)):
+                        if x in bit:
+                            tags[i] |= bit[x]
+            attrs = self._attr_cache[key] = self.index.attributes(
+                cols if nums else None, tags if pairs or not nums else None)
+        return attrs
+
+    def _search_where(self, vec, k: int, where, exclude=None):
+        """``index.search_where`` of the queries `vec` under the grammar's
+        predicates: one dict for every query or one per query."""
+        preds = [where] * vec.shape[0] if where is None or isinstance(where, dict) else list(where)
+        if len(preds) != vec.shape[0]:
+            raise ValueError(f"where: {len(preds)} predicates for {vec.shape[0]} queries")
+        nums, pairs = where_layout(preds, self._where_is_numeric)
+        attrs = self._where_attributes(nums, pairs)
+        return self.index.search_where(vec, k, attrs,
+                                       [where_predicate(p, nums, pairs) for p in preds],
+                                       exclude=exclude)
+
     # -- reads ------------------------------------------------------------------------------
     def similarity_search_with_score_by_vector(self, embedding: List[float], k: int = 4,
                                                filter: Optional[Any] = None, fetch_k: int = 20,
@@ -583,14 +763,30 @@ class FAISS:
         plain search returns a re-ingested book twice.  Documents without the
         field count one by one.  With a host `filter` the distinct search
         fetches `fetch_k` values and the filter runs after it; not together
-        with ``exact_filter`` (library-specific)."""
+        with ``exact_filter`` (library-specific).
+
+        ``where={...}``: the k nearest documents among those whose metadata
+        pass the predicate, filtered on the device inside the search
+        (``index.search_where``): exactly min(k, matches) of them.  The
+        grammar is a dict over metadata fields: a numeric field takes ``$gte
+        $lte $gt $lt $eq``, a categorical or list-valued field ``$in $all $nin
+        $neq $eq``, a bare value is ``$eq``; at most 4 numeric fields and 64
+        (field, value) pairs, anything else is a ValueError (`filter` with
+        ``exact_filter=True`` takes any predicate).  Combines with
+        ``exclude_ids``; not with ``distinct`` or ``exact_filter``
+        (library-specific)."""
         vector = np.array([embedding], dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
         exclude_ids = kwargs.get("exclude_ids")
         distinct = kwargs.get("distinct")
+        where = kwargs.get("where")
         if distinct is not None and exact_filter:
             raise ValueError("distinct and exact_filter cannot be combined")
+        if where is not None and distinct is not None:
+            raise ValueError("where and distinct cannot be combined")
+        if where is not None and exact_filter:
+            raise ValueError("where and exact_filter cannot be combined")
         drop = None
         if exclude_ids is not None:
             if exact_filter and filter is not None:
@@ -601,6 +797,9 @@ class FAISS:
             scores, indices = self.index.search_distinct(
                 vector, k if filter is None else fetch_k, self._distinct_grouping(distinct),
                 exclude=None if drop is None else [drop])
+        elif where is not None:
+            scores, indices = self._search_where(vector, k if filter is None else fetch_k, where,
+                                                 exclude=None if drop is None else [drop])
         elif drop is not None:
             scores, indices = self.index.search(vector, k if filter is None else fetch_k,
                                                 exclude=[drop])
@@ -688,14 +887,20 @@ class FAISS:
                                                              score_threshold, filter=filter)
 
     def similarity_search_batch_by_vector(self, embeddings, k: int = 4,
-                                          distinct: Optional[str] = None):
+                                          distinct: Optional[str] = None, where=None):
         """Batched variant (one engine call for many queries): list of
         [(Document, score)] per query, label -1 skipped.  ``distinct`` as in
-        ``similarity_search_with_score_by_vector``."""
+        ``similarity_search_with_score_by_vector``; ``where``: one predicate of
+        its grammar per query (or one dict for all of them), not together with
+        ``distinct``."""
         vec = np.array(embeddings, dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vec)
-        if distinct is not None:
+        if where is not None and distinct is not None:
+            raise ValueError("where and distinct cannot be combined")
+        if where is not None:
+            scores, indices = self._search_where(vec, k, where)
+        elif distinct is not None:
             scores, indices = self.index.search_distinct(vec, k,
                                                          self._distinct_grouping(distinct))
         else:
@@ -762,6 +967,8 @@ class FAISS:
                                                 fetch_k: int = 20, lambda_mult: float = 0.5,
                                                 filter: Optional[Any] = None,
                                                 **kwargs: Any) -> List[Document]:
+        if kwargs.get("where") is not None:
+            raise ValueError("where and mmr cannot be combined")
         return [d for d, _ in self.max_marginal_relevance_search_with_score_by_vector(
             embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, filter=filter,
             exact_filter=bool(kwargs.get("exact_filter", False)))]
@@ -838,7 +1045,7 @@ class FAISS:
     def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
                                key: str = "book_id",
                                mmr: Optional[Tuple[int, float]] = None,
-                               distinct: Optional[str] = None
+                               distinct: Optional[str] = None, where=None
                                ) -> List[List[Tuple[Document, float]]]:
         """The reference's per-student candidate path
         (candidate_builder.py:138-203) for many students in one device call.
@@ -864,10 +1071,23 @@ class FAISS:
         of that field (``distinct="author"``: no author twice per student): the
         means are computed on the device, come back to the host and are
         searched by ``index.search_distinct`` with the same exclusions.  Not
-        together with ``mmr``."""
+        together with ``mmr``.
+
+        ``where=[...]`` gives every profile a predicate of the ``where=``
+        grammar (``similarity_search_with_score_by_vector``; one dict: the same
+        for all): the k nearest allowed documents that pass it, filtered on
+        the device (``index.search_where`` over the means, with the same
+        exclusions).  Not together with ``mmr`` or ``distinct``."""
         if distinct is not None and mmr is not None:
             raise ValueError("distinct and mmr cannot be combined")
+        if where is not None and mmr is not None:
+            raise ValueError("where and mmr cannot be combined")
+        if where is not None and distinct is not None:
+            raise ValueError("where and distinct cannot be combined")
         profiles = list(profiles)
+        if where is not None and not isinstance(where, dict):
+            where = list(where)
+            _len_check_if_sized(profiles, where, "profiles", "where")
         if exclude is not None:
             exclude = list(exclude)
             _len_check_if_sized(profiles, exclude, "profiles", "exclude")
@@ -875,7 +1095,14 @@ class FAISS:
         kept, rows, lists = self.profile_requests(profiles, exclude, key)
         if not kept:
             return out
-        if distinct is not None:
+        if where is not None:
+            vec = self.index.mean_rows(rows)
+            if self._normalize_L2:
+                vfaiss.normalize_L2(vec)
+            scores, labels = self._search_where(
+                vec, k, where if isinstance(where, dict) else [where[p] for p in kept],
+                exclude=lists)
+        elif distinct is not None:
             vec = self.index.mean_rows(rows)
             if self._normalize_L2:
                 vfaiss.normalize_L2(vec)

@@ -50,6 +50,9 @@ extern "C" {
  * of the union, so each shard returns its raw best 2k-1 (any k) and
  * vs_merge_topk applies the rule once (vsearch/sharded.py).  No effect on L2. */
 #define VS_RAW_ORDER 4
+/* vs_search_where: skip the windows and answer every query with the
+ * predicated scan. */
+#define VS_WHERE_SCAN 8
 
 /* Status codes. */
 #define VS_OK 0
@@ -355,6 +358,86 @@ int vs_distinct_plan(int64_t k, int metric, int raw, int64_t live, int64_t* out,
  * calls' chunks of queries), and queries whose first window was too short
  * (searched again at least once). */
 int vs_distinct_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int reset);
+
+/* ---- where searches --------------------------------------------------------
+ * Exact top-k under a predicate that differs per query (pgvector WHERE, Qdrant
+ * payload filters, Milvus expr).  The reference conditions every
+ * recommendation on the reader — a reading level band, genres
+ * (src/recommendation_api/scoring.py:81-93, candidate_builder.py:187-203,
+ * mcp_book_server.py:615-682) — and filters an over-fetch of k * 2 on the host
+ * (service.py:529-542), which returns fewer than k once the predicate is
+ * selective.
+ *
+ * An attribute handle gives every label of an index up to four float32
+ * columns and one 64-bit tag word.  cols: HOST float32, column-major
+ * [ncol][n], ncol in 0 .. 4; tags: HOST uint64 [n] or NULL (all 0); entry i
+ * belongs to label id_base + i; n must equal the live row count.  A NaN
+ * column value means "unknown".  The handle keeps the attributes on the
+ * device by label and by row in place (one array when the index holds no
+ * tombstones) and the index's generation: whatever moves rows or changes
+ * labels (vs_add, vs_remove_ids, vs_reset, a pack, vs_set_id_base to another
+ * base) makes it stale ("stale attributes"); it stays valid across
+ * vs_update_rows.  Checked in this order: the output, the index, ncol, n, the
+ * columns, then n against the live rows. */
+typedef struct vs_attrs vs_attrs;
+int vs_attrs_create(vs_index* idx, int ncol, const float* cols, const uint64_t* tags, int64_t n,
+                    void* stream, vs_attrs** out);
+int vs_attrs_destroy(vs_attrs* attrs);
+/* The predicate of query q, from HOST arrays any of which may be NULL ("no
+ * test"):
+ *   lo, hi: float32 [nq][ncol].  Column c is tested unless lo == -inf and
+ *           hi == +inf; a tested column passes iff lo <= v && v <= hi, so a NaN
+ *           value fails it.  A NaN bound: VS_E_INVALID.
+ *   masks:  uint64 [nq][3] = any_of, all_of, none_of: any_of == 0 ||
+ *           (tags & any_of), (tags & all_of) == all_of, (tags & none_of) == 0.
+ * A row passes iff every test passes; lo > hi matches nothing (legal).
+ *
+ * vs_attrs_count: out[q] (HOST int64 [nq]) = the live rows that pass predicate
+ * q; one streaming kernel over the by-row arrays.  Waits for `stream`. */
+int vs_attrs_count(const vs_attrs* attrs, const float* lo, const float* hi, const uint64_t* masks,
+                   int64_t nq, int64_t* out, void* stream);
+/* What vs_search would return over an index that held only the rows that pass
+ * query q's predicate and are not in q's exclusion list (excl_offs /
+ * excl_labels as vs_search_excl, NULL: none): vs_search's order, tie rules
+ * (faiss's inner-product rule unless VS_RAW_ORDER), labels and padding;
+ * exactly min(k, allowed matches) entries.  Any k.
+ *
+ * Route A (windows): the queries are searched in raw order for a window of w
+ * entries (vs_distinct_plan's lengths), the entries whose row fails the
+ * query's predicate are dropped, and a query whose window held fewer than it
+ * needs and did not reach the end of the rows is searched again with a window
+ * four times longer, while that is at most 1,023 entries or every live row.
+ * Route B (the predicated scan): what is left is answered by the exact paged
+ * kernels with the predicate and the exclusion list tested where a row enters
+ * a query's list; batches of at most 32 queries stream the rows and skip the
+ * 4-row steps no query wants.  A call of at most 32 queries counts its
+ * predicates' rows first (vs_attrs_count's kernel) and sends a query whose
+ * passing fraction is below 0.05 to route B at once; VS_WHERE_SCAN sends every
+ * query there.  Route A returns the staged engine's keys (the fp32 rounding of
+ * the exact score), route B the exact engines' fp32 keys, inside the
+ * documented tolerance of those: a query's D bits may depend on the route.
+ *
+ * Checked before the index is read, in this order: the index, the handle,
+ * n >= 0, k > 0 and k's bound (VS_E_INVALID); n == 0 is success; the bounds
+ * (a NaN), the exclusion offsets, the buffers.  A handle of another index or
+ * an older generation: VS_E_INVALID.  flags: VS_IN_DEVICE (x), VS_OUT_DEVICE
+ * (D, I), VS_RAW_ORDER, VS_WHERE_SCAN.  The call reads a 4-byte count per
+ * round, so it waits for `stream`; a capturing stream: VS_E_UNSUPPORTED. */
+int vs_search_where(vs_index* idx, const vs_attrs* attrs, const float* x, int64_t n, int64_t k,
+                    const float* lo, const float* hi, const uint64_t* masks,
+                    const int64_t* excl_offs, const int64_t* excl_labels, float* D, int64_t* I,
+                    int flags, void* stream);
+/* Diagnostic (touches no device): the windows of a where search for k over
+ * `live` rows, round by round, then 0 for "the scan", or a last window equal
+ * to `live` when no scan is needed: out[r] for r < nmax.  Returns the number
+ * of entries of the whole plan (0 for live == 0), or VS_E_INVALID. */
+int vs_where_plan(int64_t k, int metric, int raw, int64_t live, int64_t* out, int nmax);
+/* Process-wide counters of the where searches since the last reset (reset != 0
+ * clears them): queries searched, window rounds run (summed over the calls'
+ * chunks), queries whose first window was too short, queries answered by the
+ * scan, and the rows its streaming kernel loaded. */
+int vs_where_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int64_t* scanned,
+                   int64_t* rows_streamed, int reset);
 
 /* ---- example searches ------------------------------------------------------
  * Recommendation from examples (Qdrant recommend, strategy="best_score"): the
