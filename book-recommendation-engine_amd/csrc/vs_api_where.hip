@@ -9,33 +9,9 @@
 using namespace vs;
 using namespace vs::host;
 
-namespace {
-
-// Process-wide counters (vs_where_stats): queries searched, window rounds run
-// (summed over chunks), queries searched again after their first window,
-// queries answered by the scan, rows gemv_topk_where loaded.
-std::atomic<int64_t> g_searches{0}, g_rounds{0}, g_requeried{0}, g_scanned{0}, g_streamed{0};
-
-// What the chunks of one call share.
-struct WhereCall {
-  const vs_attrs* attrs = nullptr;
-  std::vector<WherePred> hp;  // the call's predicates, by query
-  WherePred* dp = nullptr;
-  std::vector<int64_t> xoffs, xrows;  // the exclusion sets as rows in place (empty: none)
-  int64_t* dxoffs = nullptr;
-  int64_t* dxrows = nullptr;
-  bool scan_only = false;    // VS_WHERE_SCAN
-  bool count_first = false;  // a small call: count, then choose the route per query
-  bool excl() const { return !xrows.empty(); }
-};
-
-// The passing fraction below which a counted query goes to the scan at once.
-// Env VS_WHERE_CROSSOVER (read at every search, for tools/bench_where.py's A/B
-// runs: 0 keeps every counted query on the windows, 2 scans them all).
-double where_crossover() {
-  const char* e = getenv("VS_WHERE_CROSSOVER");
-  return e ? atof(e) : kWhereCrossover;
-}
+// What vs_api_boost.hip shares with this unit (declared in vs_host.h).
+namespace vs {
+namespace host {
 
 int check_bounds(const char* what, const float* lo, const float* hi, int64_t n, int ncol) {
   for (int64_t i = 0; i < n * ncol; ++i)
@@ -64,24 +40,22 @@ void build_preds(const float* lo, const float* hi, const uint64_t* masks, int64_
 
 // The staged queries list[0 .. cnt) (device) of chunk `a` as a batch of their own.
 int gather_batch(const vs_index* idx, const SearchArgs& a, const int* list, int cnt, Scratch& scr,
-                 SearchArgs* b, hipStream_t st) {
+                 SearchArgs* b, hipStream_t st, const char* what) {
   const size_t rowb = (size_t)idx->ld * sizeof(float);
   const int nq_pad = (int)round_up(std::max<int64_t>(cnt, kGemvMaxQ), kBQ);
   float* gq = nullptr;
   float* gaux = nullptr;
   uint16_t* gq16 = nullptr;
-  VS_HIP(scr.alloc((void**)&gq, (size_t)nq_pad * rowb), "vs_search_where: scratch");
+  VS_HIPW(scr.alloc((void**)&gq, (size_t)nq_pad * rowb), what, ": scratch");
   if (a.mode == MODE_L2)
-    VS_HIP(scr.alloc((void**)&gaux, (size_t)nq_pad * sizeof(float)), "vs_search_where: scratch");
-  VS_HIP(launch_excl_gather(a.qbuf, (int64_t)rowb, a.mode == MODE_L2 ? a.qaux : nullptr, list, cnt,
-                            nq_pad, gq, gaux, st),
-         "vs_search_where: gather launch");
+    VS_HIPW(scr.alloc((void**)&gaux, (size_t)nq_pad * sizeof(float)), what, ": scratch");
+  VS_HIPW(launch_excl_gather(a.qbuf, (int64_t)rowb, a.mode == MODE_L2 ? a.qaux : nullptr, list, cnt,
+                            nq_pad, gq, gaux, st), what, ": gather launch");
   *b = a;
   if (a.qb16) {
-    VS_HIP(scr.alloc((void**)&gq16, (size_t)nq_pad * rowb / 2), "vs_search_where: scratch");
-    VS_HIP(launch_excl_gather(a.qb16, (int64_t)rowb / 2, nullptr, list, cnt, nq_pad, gq16, nullptr,
-                              st),
-           "vs_search_where: gather launch");
+    VS_HIPW(scr.alloc((void**)&gq16, (size_t)nq_pad * rowb / 2), what, ": scratch");
+    VS_HIPW(launch_excl_gather(a.qb16, (int64_t)rowb / 2, nullptr, list, cnt, nq_pad, gq16, nullptr,
+                              st), what, ": gather launch");
     b->qb16 = gq16;
   }
   b->qbuf = gq;
@@ -93,22 +67,65 @@ int gather_batch(const vs_index* idx, const SearchArgs& a, const int* list, int 
 
 // The exclusion sets of the chunk's queries `list` (c0: the chunk's first
 // query) as a CSR by slot.
-void slot_excl(const WhereCall& c, int64_t c0, const std::vector<int>& list,
-               std::vector<int64_t>* offs, std::vector<int64_t>* rows) {
+void slot_excl(const std::vector<int64_t>& xoffs, const std::vector<int64_t>& xrows, int64_t c0,
+               const std::vector<int>& list, std::vector<int64_t>* offs,
+               std::vector<int64_t>* rows) {
   offs->assign(list.size() + 1, 0);
   rows->clear();
   for (size_t s = 0; s < list.size(); ++s) {
     const size_t q = (size_t)(c0 + list[s]);
-    rows->insert(rows->end(), c.xrows.begin() + c.xoffs[q], c.xrows.begin() + c.xoffs[q + 1]);
+    rows->insert(rows->end(), xrows.begin() + xoffs[q], xrows.begin() + xoffs[q + 1]);
     (*offs)[s + 1] = (int64_t)rows->size();
   }
 }
 
-int upload(Scratch& scr, const void* src, size_t bytes, void** dst, hipStream_t st) {
-  VS_HIP(scr.alloc(dst, std::max<size_t>(bytes, 8)), "vs_search_where: scratch");
+int upload(Scratch& scr, const void* src, size_t bytes, void** dst, hipStream_t st,
+           const char* what) {
+  VS_HIPW(scr.alloc(dst, std::max<size_t>(bytes, 8)), what, ": scratch");
   if (bytes)
-    VS_HIP(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st), "vs_search_where: upload");
+    VS_HIPW(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st), what, ": upload");
   return VS_OK;
+}
+
+// The checks of a handle against its index; the caller holds the reader lock.
+int check_attrs(const char* what, const vs_index* idx, const vs_attrs* at) {
+  if (at->idx != idx)
+    return fail(VS_E_INVALID, std::string(what) + ": the attributes belong to another index");
+  if (at->gen != idx->gen)
+    return fail(VS_E_INVALID,
+                std::string(what) + ": stale attributes (the index changed since they were built)");
+  return VS_OK;
+}
+
+}  // namespace host
+}  // namespace vs
+
+namespace {
+
+// Process-wide counters (vs_where_stats): queries searched, window rounds run
+// (summed over chunks), queries searched again after their first window,
+// queries answered by the scan, rows gemv_topk_where loaded.
+std::atomic<int64_t> g_searches{0}, g_rounds{0}, g_requeried{0}, g_scanned{0}, g_streamed{0};
+
+// What the chunks of one call share.
+struct WhereCall {
+  const vs_attrs* attrs = nullptr;
+  std::vector<WherePred> hp;  // the call's predicates, by query
+  WherePred* dp = nullptr;
+  std::vector<int64_t> xoffs, xrows;  // the exclusion sets as rows in place (empty: none)
+  int64_t* dxoffs = nullptr;
+  int64_t* dxrows = nullptr;
+  bool scan_only = false;    // VS_WHERE_SCAN
+  bool count_first = false;  // a small call: count, then choose the route per query
+  bool excl() const { return !xrows.empty(); }
+};
+
+// The passing fraction below which a counted query goes to the scan at once.
+// Env VS_WHERE_CROSSOVER (read at every search, for tools/bench_where.py's A/B
+// runs: 0 keeps every counted query on the windows, 2 scans them all).
+double where_crossover() {
+  const char* e = getenv("VS_WHERE_CROSSOVER");
+  return e ? atof(e) : kWhereCrossover;
 }
 
 // Route B over batch `b` (its nq queries staged and padded; results by slot in
@@ -274,7 +291,7 @@ int run_scan(vs_index* idx, const WhereCall& c, const SearchArgs& a, int64_t c0,
   int64_t* dxo = nullptr;
   int64_t* dxr = nullptr;
   if (c.excl()) {
-    slot_excl(c, c0, sl, &soffs, &srows);
+    slot_excl(c.xoffs, c.xrows, c0, sl, &soffs, &srows);
     rc = upload(scr, soffs.data(), soffs.size() * sizeof(int64_t), (void**)&dxo, st);
     if (!rc) rc = upload(scr, srows.data(), srows.size() * sizeof(int64_t), (void**)&dxr, st);
     if (rc) return rc;
@@ -369,7 +386,7 @@ int run_where(vs_index* idx, const WhereCall& c, const SearchArgs& a, int64_t c0
       if (rc) return rc;
       uploads = true;
       if (c.excl()) {
-        slot_excl(c, c0, cur, &soffs, &srows);
+        slot_excl(c.xoffs, c.xrows, c0, cur, &soffs, &srows);
         int64_t* d1 = nullptr;
         int64_t* d2 = nullptr;
         rc = upload(rs, soffs.data(), soffs.size() * sizeof(int64_t), (void**)&d1, st);
@@ -456,16 +473,6 @@ void free_attrs(vs_attrs* a) {
   if (a->lcols) (void)hipFree(a->lcols);
   if (a->ltags) (void)hipFree(a->ltags);
   delete a;
-}
-
-// The checks of a handle against its index; the caller holds the reader lock.
-int check_attrs(const char* what, const vs_index* idx, const vs_attrs* at) {
-  if (at->idx != idx)
-    return fail(VS_E_INVALID, std::string(what) + ": the attributes belong to another index");
-  if (at->gen != idx->gen)
-    return fail(VS_E_INVALID,
-                std::string(what) + ": stale attributes (the index changed since they were built)");
-  return VS_OK;
 }
 
 }  // namespace

@@ -642,6 +642,39 @@ inline int where_windows(int64_t need, int64_t live, int64_t* out, int nmax, boo
   }
   return n;
 }
+// What vs_api_where.hip defines for vs_api_boost.hip too (`what`: the entry
+// point's name, the prefix of every message).
+// A NaN in lo / hi ([n][ncol], either may be null) is VS_E_INVALID.
+int check_bounds(const char* what, const float* lo, const float* hi, int64_t n, int ncol);
+// The n predicates of a call's where arrays (all null: every live row passes).
+void build_preds(const float* lo, const float* hi, const uint64_t* masks, int64_t n, int ncol,
+                 std::vector<vs::WherePred>* out);
+// The staged queries list[0 .. cnt) (device) of chunk `a` as a batch of their own.
+int gather_batch(const vs_index* idx, const SearchArgs& a, const int* list, int cnt, Scratch& scr,
+                 SearchArgs* b, hipStream_t st, const char* what = "vs_search_where");
+// The exclusion sets (CSR xoffs / xrows by the call's query) of the chunk's
+// queries `list` (c0: the chunk's first query) as a CSR by slot.
+void slot_excl(const std::vector<int64_t>& xoffs, const std::vector<int64_t>& xrows, int64_t c0,
+               const std::vector<int>& list, std::vector<int64_t>* offs,
+               std::vector<int64_t>* rows);
+// *dst = scratch holding the `bytes` at src (copied on `st`; src must live
+// until the stream has passed the copy).
+int upload(Scratch& scr, const void* src, size_t bytes, void** dst, hipStream_t st,
+           const char* what = "vs_search_where");
+// The checks of an attribute handle against its index (foreign, stale); the
+// caller holds the reader lock.
+int check_attrs(const char* what, const vs_index* idx, const vs_attrs* at);
+
+// ---- boosted searches (vs_api_boost.hip) ---------------------------------------
+// The give-up rule of route A: after a round, a query whose deficit
+// final_key[k-1] - fl32(K_w - U) exceeds kBoostGiveUp times the window's own
+// raw key spread K_w - K_0 goes to the scan at once instead of to a window four
+// times longer.  A cost rule only (the scan is exact).  Env VS_BOOST_GIVEUP
+// (read at every search, for tools/bench_boost.py's A/B runs; a negative value
+// runs every window before the scan).  1.0 is the starting value: the A/B on a
+// 10M-row corpus that DESIGN.md section 7 "Boosted searches" describes has not
+// been run yet, so it is neither confirmed nor replaced.
+constexpr double kBoostGiveUp = 1.0;
 
 }  // namespace host
 }  // namespace vs

@@ -827,4 +827,42 @@ struct GemvWhereArgs {
 hipError_t launch_gemv_topk_where(int mode, int nq, const GemvWhereArgs& a, Partials part,
                                   hipStream_t st);
 
+// Boosted searches (vs_boost.hip; vs_api_boost.hip vs_search_boost): exact
+// top-k by final_key = fl32(key - b), b a per-query function of the row's
+// attributes (boost_value, vs_boost_value.h).
+constexpr int kBoostMaxTags = 4;
+constexpr int kBoostMaxWindow = 1023;  // boost_rerank sorts a window in LDS
+// One query's boost: column c contributes by kind[c] (0 none, 1 near, 2 ramp)
+// with (t, s, w, miss)[c]; tag term j adds bonus[j] when (tags & mask[j]) != 0;
+// U >= b >= L for every row (boost_bounds).
+struct BoostSpec {
+  float t[kWhereMaxCols], s[kWhereMaxCols], w[kWhereMaxCols], miss[kWhereMaxCols];
+  unsigned long long mask[kBoostMaxTags];
+  float bonus[kBoostMaxTags];
+  float U, L;
+  unsigned char kind[kWhereMaxCols];
+  unsigned pad;
+};
+static_assert(sizeof(BoostSpec) == 128, "thirty-two dwords");
+// Route A: slot s of Din / Iin ([ns][w], w <= kBoostMaxWindow, raw entries as
+// launch_where_drop reads them) is query q = qmap ? qmap[s] : s.  The entries
+// whose row passes preds[q] are ranked by (final_key, label); the first k go to
+// row s of Dout / Iout ([ns][k], padded).  state[q] = 0 when the slot is
+// settled (the window reached the end of the rows, or k entries were kept and
+// final_key[k-1] < fl32(K_w - U) with K_w the window's last raw key), else 1,
+// or 2 when its deficit final_key[k-1] - fl32(K_w - U) exceeds giveup times the
+// window's raw key spread K_w - K_0 (giveup < 0: never).  deficit / spread
+// (optional, by query): those two values.
+hipError_t launch_boost_rerank(int mode, const float* Din, const int64_t* Iin, int ns, int w,
+                               const WhereAttrs& at, const WherePred* preds,
+                               const BoostSpec* specs, const int* qmap, int64_t id_base, int k,
+                               bool w_is_all, float giveup, float* Dout, int64_t* Iout,
+                               int* state, float* deficit, float* spread, hipStream_t st);
+// Route B: launch_gemm_topk_where / launch_gemv_topk_where with the lists, the
+// floors and the partials in final keys; specs is indexed like preds.
+hipError_t launch_gemm_topk_boost(int mode, const GemmWhereArgs& a, const BoostSpec* specs,
+                                  Partials part, hipStream_t st);
+hipError_t launch_gemv_topk_boost(int mode, int nq, const GemvWhereArgs& a,
+                                  const BoostSpec* specs, Partials part, hipStream_t st);
+
 }  // namespace vs

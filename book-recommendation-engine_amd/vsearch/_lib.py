@@ -23,6 +23,7 @@ IN_DEVICE = 1
 OUT_DEVICE = 2
 RAW_ORDER = 4
 WHERE_SCAN = 8
+BOOST_SCAN = 16
 MAX_K = 64
 ENGINE_AUTO = 0
 ENGINE_FP32_MFMA = 1
@@ -84,6 +85,10 @@ SIGNATURES = {
                                  _c_int, _vp]),
     "vs_where_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _vp, _c_int]),
     "vs_where_stats": (_c_int, [_i64p, _i64p, _i64p, _i64p, _i64p, _c_int]),
+    "vs_search_boost": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "vs_boost_eval": (_c_int, [_c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+    "vs_boost_stats": (_c_int, [_i64p, _i64p, _i64p, _i64p, _c_int]),
     "vs_search_examples": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
                                     _vp, _vp, _c_int, _vp]),
     "vs_search_examples_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp,

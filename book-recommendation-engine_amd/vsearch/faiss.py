@@ -587,6 +587,117 @@ def where_stats(reset: bool = False):
     return tuple(x.value for x in v)
 
 
+MAX_BOOST_TAGS = 4
+BOOST_KINDS = {"near": 1, "ramp": 2}
+
+
+def boost_arrays(boost, ncol: int, nq: int):
+    """The arrays of ``vs_search_boost`` for ``nq`` queries over ``ncol``
+    numeric columns: ``(kinds, params, tag_masks, tag_bonus)`` = int32
+    (nq, ncol), float32 (nq, ncol, 4) holding t, s, w, miss, uint64 (nq, 4),
+    float32 (nq, 4).
+
+    ``boost`` is one spec for every query or a sequence of ``nq`` of them.  A
+    spec is ``None`` (no boost) or a mapping with the optional keys
+    ``"columns"`` — one entry per column: ``None``, ``("near", t, s, w[, miss])``
+    = ``w * max(0, 1 - |v - t| / s)`` or ``("ramp", t, s, w[, miss])`` =
+    ``w * min(1, max(0, (v - t) / s))``, ``miss`` (default 0) the term of a NaN
+    value — and ``"tags"`` — up to four ``(mask, bonus)`` pairs, ``bonus`` added
+    when the row's tag word shares a bit with ``mask``.  A 4-tuple of arrays of
+    those shapes passes through."""
+    ncol, nq = int(ncol), int(nq)
+    if isinstance(boost, tuple) and len(boost) == 4 and isinstance(boost[0], np.ndarray):
+        kinds = np.ascontiguousarray(boost[0], dtype=np.int32).reshape(nq, ncol)
+        params = np.ascontiguousarray(boost[1], dtype=np.float32).reshape(nq, ncol, 4)
+        tag_masks = np.ascontiguousarray(boost[2], dtype=np.uint64).reshape(nq, MAX_BOOST_TAGS)
+        tag_bonus = np.ascontiguousarray(boost[3], dtype=np.float32).reshape(nq, MAX_BOOST_TAGS)
+    else:
+        specs = [boost] * nq if boost is None or isinstance(boost, dict) else list(boost)
+        if len(specs) != nq:
+            raise ValueError(f"boost: {len(specs)} specs for {nq} queries")
+        kinds = np.zeros((nq, ncol), dtype=np.int32)
+        params = np.zeros((nq, ncol, 4), dtype=np.float32)
+        params[:, :, 1] = 1.0
+        tag_masks = np.zeros((nq, MAX_BOOST_TAGS), dtype=np.uint64)
+        tag_bonus = np.zeros((nq, MAX_BOOST_TAGS), dtype=np.float32)
+        for q, sp in enumerate(specs):
+            if sp is None:
+                continue
+            unknown = set(sp) - {"columns", "tags"}
+            if unknown:
+                raise ValueError(f"boost: unknown keys {sorted(unknown)}")
+            cols = sp.get("columns")
+            if cols is not None:
+                cols = list(cols)
+                if len(cols) != ncol:
+                    raise ValueError(f"boost: columns holds {len(cols)} entries for {ncol} columns")
+                for c, term in enumerate(cols):
+                    if term is None:
+                        continue
+                    term = tuple(term)
+                    if len(term) not in (4, 5) or term[0] not in BOOST_KINDS:
+                        raise ValueError("boost: a column term is None, (\"near\", t, s, w[, miss]) "
+                                         "or (\"ramp\", t, s, w[, miss])")
+                    kinds[q, c] = BOOST_KINDS[term[0]]
+                    params[q, c, :3] = term[1:4]
+                    params[q, c, 3] = term[4] if len(term) == 5 else 0.0
+            tags = list(sp.get("tags") or ())
+            if len(tags) > MAX_BOOST_TAGS:
+                raise ValueError(f"boost: more than {MAX_BOOST_TAGS} tag terms")
+            for j, (mask, bonus) in enumerate(tags):
+                tag_masks[q, j] = np.uint64(int(mask) & (2**64 - 1))
+                tag_bonus[q, j] = bonus
+    if not (np.isfinite(params).all() and np.isfinite(tag_bonus).all()):
+        raise ValueError("boost: a parameter that is not finite")
+    if not (params[:, :, 1] > 0).all():
+        raise ValueError("boost: a scale s must be > 0")
+    if ((kinds < 0) | (kinds > 2)).any():
+        raise ValueError("boost: a kind must be 0, 1 or 2")
+    return kinds, params, tag_masks, tag_bonus
+
+
+def boost_eval(columns, tags, boost, nq: int | None = None):
+    """``(b, bounds)``: the boost of every (query, row) as the device computes
+    it, float32 (nq, nrows), and each query's ``(L, U)`` with ``L <= b <= U``,
+    float32 (nq, 2) (vs_boost_eval; touches no device).  ``columns``: up to
+    four sequences of one value per row (NaN: unknown) or ``None``; ``tags``:
+    one 64-bit word per row or ``None``; ``boost`` as in ``boost_arrays``."""
+    cols = np.zeros((0, 0), dtype=np.float32) if columns is None else \
+        np.ascontiguousarray(columns, dtype=np.float32)
+    if cols.ndim == 1:
+        cols = cols.reshape(1, -1) if cols.size else cols.reshape(0, 0)
+    if cols.ndim != 2 or cols.shape[0] > MAX_WHERE_COLUMNS:
+        raise ValueError(f"boost_eval: at most {MAX_WHERE_COLUMNS} columns of one value per row")
+    ncol = int(cols.shape[0])
+    if tags is not None:
+        tags = np.ascontiguousarray(tags, dtype=np.uint64).reshape(-1)
+    nrows = int(cols.shape[1]) if ncol else (int(tags.size) if tags is not None else 0)
+    if tags is not None and tags.size != nrows:
+        raise ValueError(f"boost_eval: {tags.size} tags for {nrows} rows")
+    if nq is None:
+        nq = 1 if boost is None or isinstance(boost, dict) else \
+            (int(np.asarray(boost[2]).reshape(-1, MAX_BOOST_TAGS).shape[0])
+             if isinstance(boost, tuple) else len(boost))
+    kinds, params, tag_masks, tag_bonus = boost_arrays(boost, ncol, nq)
+    b = np.zeros((nq, nrows), dtype=np.float32)
+    bounds = np.zeros((nq, 2), dtype=np.float32)
+    _lib.check(_lib.load().vs_boost_eval(
+        ncol, _ptr(cols), _ptr(tags) if tags is not None else None, nrows, _ptr(kinds),
+        _ptr(params), _ptr(tag_masks), _ptr(tag_bonus), nq, _ptr(b), _ptr(bounds)),
+        "vs_boost_eval")
+    return b, bounds
+
+
+def boost_stats(reset: bool = False):
+    """(queries searched, window rounds run, queries searched again, queries
+    answered by the scan) of the boosted searches of this process since the
+    last reset."""
+    v = [ctypes.c_int64(0) for _ in range(4)]
+    _lib.check(_lib.load().vs_boost_stats(*[ctypes.byref(x) for x in v], 1 if reset else 0),
+               "vs_boost_stats")
+    return tuple(x.value for x in v)
+
+
 class Index:
     """Common base (faiss.Index)."""
 
@@ -923,6 +1034,55 @@ class IndexFlat(Index):
             self._h, attrs._h, ctypes.c_void_p(xq_ptr), int(n), int(k), _ptr(lo), _ptr(hi),
             _ptr(masks), None, None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags,
             ctypes.c_void_p(stream)), "vs_search_where")
+
+    def search_boost(self, x, k, attrs: Attributes, boost, *, where=None, exclude=None,
+                     scan: bool = False):
+        """The k rows with the best boosted score, exactly: every live row is
+        ranked by ``fl32(key - b)``, key the engine's key (-score for inner
+        product, the squared distance for L2) and b the query's boost of the
+        row's attributes (``boost_arrays``; ``boost_eval`` returns its bits),
+        ties to the lower label.  D is ``score + b`` for inner product and
+        ``distance - b`` for L2 (it may be negative).  ``where`` (as in
+        ``search_where``) and ``exclude`` (as in ``search``) remove rows from
+        the candidates.  ``scan=True`` skips the windows and answers every
+        query with the boosted scan."""
+        x = _as_f32_rows(x)
+        n, d = x.shape
+        assert d == self._d
+        k = int(k)
+        assert k > 0
+        if attrs.index is not self:
+            raise ValueError("the Attributes belong to another index")
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        kinds, params, tmasks, tbonus = boost_arrays(boost, attrs.ncol, n)
+        lo, hi, masks = (None, None, None) if where is None else where_arrays(where, attrs.ncol, n)
+        offs, labels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+        _lib.check(self._lib.vs_search_boost(
+            self._h, attrs._h, _ptr(x), n, k, _ptr(kinds), _ptr(params), _ptr(tmasks), _ptr(tbonus),
+            _ptr(lo) if lo is not None else None, _ptr(hi) if hi is not None else None,
+            _ptr(masks) if masks is not None else None,
+            offs.ctypes.data if offs is not None else None,
+            _ptr(labels) if labels is not None else None, _ptr(D), _ptr(I),
+            _lib.BOOST_SCAN if scan else 0, None), "vs_search_boost")
+        return D, I
+
+    def search_boost_device(self, xq_ptr: int, n: int, k: int, attrs: Attributes, boost,
+                            D_ptr: int, I_ptr: int, stream: int = 0, where=None,
+                            scan: bool = False) -> None:
+        """``search_boost`` with the queries and the results on this index's
+        device, on `stream` (the call waits for the stream after every round; a
+        capturing stream is refused).  The boosts and predicates stay host
+        arrays."""
+        kinds, params, tmasks, tbonus = boost_arrays(boost, attrs.ncol, n)
+        lo, hi, masks = (None, None, None) if where is None else where_arrays(where, attrs.ncol, n)
+        flags = _lib.IN_DEVICE | _lib.OUT_DEVICE | (_lib.BOOST_SCAN if scan else 0)
+        _lib.check(self._lib.vs_search_boost(
+            self._h, attrs._h, ctypes.c_void_p(xq_ptr), int(n), int(k), _ptr(kinds), _ptr(params),
+            _ptr(tmasks), _ptr(tbonus), _ptr(lo) if lo is not None else None,
+            _ptr(hi) if hi is not None else None, _ptr(masks) if masks is not None else None,
+            None, None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags,
+            ctypes.c_void_p(stream)), "vs_search_boost")
 
     def _examples_args(self, positive, negative):
         poffs, plab, pvec = examples_csr(positive, None, self._d)

@@ -37,6 +37,10 @@ types and error behaviour:
   the search on the device (``index.search_where``), where the reference
   filters an over-fetch on the host (candidate_builder.py:187-203,
   service.py:529-542, mcp_book_server.py:615-682).
+* ``boost=`` (library-specific) — similarity plus a per-query boost of the
+  documents' metadata (reading-level match, staff pick), ranked over every
+  document on the device (``index.search_boost``), where the reference adds
+  those terms to the ``k * 2`` nearest only (scoring.py:78-131).
 """
 
 from __future__ import annotations
@@ -311,6 +315,114 @@ def where_predicate(pred, nums: Sequence[str], pairs: Sequence[Tuple[str, Any]])
         else:
             masks["any_of"] = bits
     return dict(lo=lo, hi=hi, **masks)
+
+
+# ``boost=``: the grammar of the boosted search (``index.search_boost``).  A
+# spec is a dict over metadata fields.  A numeric field takes
+# {"$near": t, "scale": s, "weight": w[, "missing": m]} (w at t, falling to 0
+# at distance s) or {"$ramp": [from, to], "weight": w[, "missing": m]} (0 at
+# `from`, w from `to` on); m (default 0) is the term of a document without
+# the field.  A categorical or list-valued field takes {"$in": [...],
+# "weight": w} or {"$eq": v, "weight": w}: w when the document holds one of
+# the values.
+BOOST_MAX_TAGS = vfaiss.MAX_BOOST_TAGS
+_BOOST_NUM_KEYS = {"$near": {"$near", "scale", "weight", "missing"},
+                   "$ramp": {"$ramp", "weight", "missing"}}
+_BOOST_TAG_KEYS = {"$in": {"$in", "weight"}, "$eq": {"$eq", "weight"}}
+
+
+def _boost_terms(spec: Any, is_numeric: Callable[[str], bool]):
+    """[(field, operator, term dict, numeric?)] of one spec, checked."""
+    if not isinstance(spec, dict):
+        raise ValueError("boost: a spec is a dict over metadata fields")
+    out = []
+    for field, term in spec.items():
+        if isinstance(field, str) and field.startswith("$"):
+            raise ValueError(f"boost: operator {field} is not supported")
+        if not isinstance(term, dict):
+            raise ValueError(f"boost: {field!r} takes a dict with an operator and a weight")
+        numeric = is_numeric(field)
+        table = _BOOST_NUM_KEYS if numeric else _BOOST_TAG_KEYS
+        ops = [key for key in term if isinstance(key, str) and key.startswith("$")]
+        if len(ops) != 1 or ops[0] not in table:
+            raise ValueError(f"boost: {field!r} takes one of {sorted(table)}"
+                             f" ({'a numeric' if numeric else 'a categorical'} field), got "
+                             f"{sorted(ops)}")
+        op = ops[0]
+        unknown = set(term) - table[op]
+        if unknown:
+            raise ValueError(f"boost: unknown keys {sorted(unknown, key=repr)} on {field!r}")
+        if not _is_number(term.get("weight")):
+            raise ValueError(f"boost: {field!r} needs a numeric weight")
+        if numeric:
+            if op == "$near" and not (_is_number(term["$near"]) and _is_number(term.get("scale"))):
+                raise ValueError(f"boost: {field!r} $near takes a number and a numeric scale")
+            if op == "$ramp" and not (isinstance(term["$ramp"], (list, tuple))
+                                      and len(term["$ramp"]) == 2
+                                      and all(_is_number(v) for v in term["$ramp"])):
+                raise ValueError(f"boost: {field!r} $ramp takes [from, to]")
+            if not _is_number(term.get("missing", 0.0)):
+                raise ValueError(f"boost: {field!r} missing takes a number")
+        elif op == "$in" and not isinstance(term["$in"], (list, tuple, set, frozenset)):
+            raise ValueError("boost: $in takes a list of values")
+        out.append((field, op, term, numeric))
+    return out
+
+
+def boost_layout(specs, is_numeric: Callable[[str], bool]):
+    """What the boost specs need of an attribute handle, as ``where_layout``:
+    (the numeric fields, the (field, value) pairs), both sorted.  More than 4
+    numeric fields, more than 4 tag terms in one spec or an operator outside
+    the grammar is a ValueError."""
+    nums: List[str] = []
+    pairs: List[Tuple[str, Any]] = []
+    for spec in specs:
+        if spec is None:
+            continue
+        ntag = 0
+        for field, op, term, numeric in _boost_terms(spec, is_numeric):
+            if numeric:
+                if field not in nums:
+                    nums.append(field)
+                continue
+            ntag += 1
+            for v in (list(term["$in"]) if op == "$in" else [term["$eq"]]):
+                if (field, v) not in pairs:
+                    pairs.append((field, v))
+        if ntag > BOOST_MAX_TAGS:
+            raise ValueError(f"boost: more than {BOOST_MAX_TAGS} categorical terms in one spec")
+    if len(nums) > vfaiss.MAX_WHERE_COLUMNS:
+        raise ValueError(f"boost: more than {vfaiss.MAX_WHERE_COLUMNS} numeric fields")
+    if len(pairs) > WHERE_MAX_PAIRS:
+        raise ValueError(f"boost: more than {WHERE_MAX_PAIRS} (field, value) pairs")
+    return tuple(sorted(nums)), tuple(sorted(pairs, key=repr))
+
+
+def boost_spec(spec, nums: Sequence[str], pairs: Sequence[Tuple[str, Any]],
+               is_numeric: Callable[[str], bool]) -> Optional[dict]:
+    """One spec of the grammar as ``index.search_boost`` takes it
+    (``vfaiss.boost_arrays``), over the columns ``nums`` and the tag bits
+    ``pairs`` of the handle."""
+    if spec is None:
+        return None
+    columns: List[Any] = [None] * len(nums)
+    tags = []
+    for field, op, term, numeric in _boost_terms(spec, is_numeric):
+        w = float(term["weight"])
+        if numeric:
+            miss = float(term.get("missing", 0.0))
+            if op == "$near":
+                columns[nums.index(field)] = ("near", float(term["$near"]), float(term["scale"]),
+                                              w, miss)
+            else:
+                lo, hi = (float(v) for v in term["$ramp"])
+                columns[nums.index(field)] = ("ramp", lo, hi - lo, w, miss)
+            continue
+        bits = 0
+        for v in (list(term["$in"]) if op == "$in" else [term["$eq"]]):
+            bits |= 1 << pairs.index((field, v))
+        tags.append((bits, w))
+    return {"columns": columns, "tags": tags}
 
 
 class FAISS:
@@ -744,6 +856,34 @@ class FAISS:
                                        [where_predicate(p, nums, pairs) for p in preds],
                                        exclude=exclude)
 
+    def _search_boost(self, vec, k: int, boost, where=None, exclude=None):
+        """``index.search_boost`` of the queries `vec` under the grammar's
+        boost specs (one dict for every query or one per query), composed with
+        ``where`` predicates and exclusion lists.  One attribute handle serves
+        the fields of both grammars."""
+        n = vec.shape[0]
+        specs = [boost] * n if boost is None or isinstance(boost, dict) else list(boost)
+        if len(specs) != n:
+            raise ValueError(f"boost: {len(specs)} specs for {n} queries")
+        preds = [where] * n if where is None or isinstance(where, dict) else list(where)
+        if len(preds) != n:
+            raise ValueError(f"where: {len(preds)} predicates for {n} queries")
+        bnums, bpairs = boost_layout(specs, self._where_is_numeric)
+        wnums, wpairs = where_layout(preds, self._where_is_numeric)
+        nums = tuple(sorted(set(bnums) | set(wnums)))
+        pairs = tuple(sorted(set(bpairs) | set(wpairs), key=repr))
+        if len(nums) > vfaiss.MAX_WHERE_COLUMNS:
+            raise ValueError(f"boost and where: more than {vfaiss.MAX_WHERE_COLUMNS} numeric "
+                             "fields together")
+        if len(pairs) > WHERE_MAX_PAIRS:
+            raise ValueError(f"boost and where: more than {WHERE_MAX_PAIRS} (field, value) pairs "
+                             "together")
+        attrs = self._where_attributes(nums, pairs)
+        return self.index.search_boost(
+            vec, k, attrs, [boost_spec(sp, nums, pairs, self._where_is_numeric) for sp in specs],
+            where=None if where is None else [where_predicate(p, nums, pairs) for p in preds],
+            exclude=exclude)
+
     # -- reads ------------------------------------------------------------------------------
     def similarity_search_with_score_by_vector(self, embedding: List[float], k: int = 4,
                                                filter: Optional[Any] = None, fetch_k: int = 20,
@@ -774,7 +914,21 @@ class FAISS:
         (field, value) pairs, anything else is a ValueError (`filter` with
         ``exact_filter=True`` takes any predicate).  Combines with
         ``exclude_ids``; not with ``distinct`` or ``exact_filter``
-        (library-specific)."""
+        (library-specific).
+
+        ``boost={...}``: the k documents with the best similarity plus a
+        boost of their metadata, ranked over every document on the device
+        (``index.search_boost``) instead of re-scoring the ``k * 2`` nearest as
+        the reference's ``score_candidates`` does.  A numeric field takes
+        ``{"$near": t, "scale": s, "weight": w, "missing": m}`` (w at t,
+        falling linearly to 0 at distance s; m for a document without the
+        field) or ``{"$ramp": [from, to], "weight": w}``; a categorical or
+        list-valued field ``{"$in": [...], "weight": w}`` or ``{"$eq": v,
+        "weight": w}``.  At most 4 numeric fields and 4 categorical terms.  The
+        returned scores are the boosted ones (score + boost for an
+        inner-product store, distance - boost for an L2 store).  Combines with
+        ``where`` and ``exclude_ids``; with ``distinct``, `filter` or MMR it is
+        a ValueError (library-specific)."""
         vector = np.array([embedding], dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vector)
@@ -787,13 +941,20 @@ class FAISS:
             raise ValueError("where and distinct cannot be combined")
         if where is not None and exact_filter:
             raise ValueError("where and exact_filter cannot be combined")
+        boost = kwargs.get("boost")
+        if boost is not None and (distinct is not None or filter is not None or exact_filter):
+            raise ValueError("boost cannot be combined with distinct or filter (not built); "
+                             "where= and exclude_ids compose with it")
         drop = None
         if exclude_ids is not None:
             if exact_filter and filter is not None:
                 raise ValueError("exclude_ids and exact_filter cannot be combined")
             wanted = set(exclude_ids)
             drop = [i for i, id_ in self.index_to_docstore_id.items() if id_ in wanted]
-        if distinct is not None:
+        if boost is not None:
+            scores, indices = self._search_boost(vector, k, boost, where=where,
+                                                 exclude=None if drop is None else [drop])
+        elif distinct is not None:
             scores, indices = self.index.search_distinct(
                 vector, k if filter is None else fetch_k, self._distinct_grouping(distinct),
                 exclude=None if drop is None else [drop])
@@ -887,18 +1048,24 @@ class FAISS:
                                                              score_threshold, filter=filter)
 
     def similarity_search_batch_by_vector(self, embeddings, k: int = 4,
-                                          distinct: Optional[str] = None, where=None):
+                                          distinct: Optional[str] = None, where=None,
+                                          boost=None):
         """Batched variant (one engine call for many queries): list of
         [(Document, score)] per query, label -1 skipped.  ``distinct`` as in
         ``similarity_search_with_score_by_vector``; ``where``: one predicate of
         its grammar per query (or one dict for all of them), not together with
-        ``distinct``."""
+        ``distinct``; ``boost``: one boost spec per query (or one dict for all
+        of them), with ``where`` or alone, not together with ``distinct``."""
         vec = np.array(embeddings, dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vec)
         if where is not None and distinct is not None:
             raise ValueError("where and distinct cannot be combined")
-        if where is not None:
+        if boost is not None and distinct is not None:
+            raise ValueError("boost and distinct cannot be combined (not built)")
+        if boost is not None:
+            scores, indices = self._search_boost(vec, k, boost, where=where)
+        elif where is not None:
             scores, indices = self._search_where(vec, k, where)
         elif distinct is not None:
             scores, indices = self.index.search_distinct(vec, k,
@@ -969,6 +1136,8 @@ class FAISS:
                                                 **kwargs: Any) -> List[Document]:
         if kwargs.get("where") is not None:
             raise ValueError("where and mmr cannot be combined")
+        if kwargs.get("boost") is not None:
+            raise ValueError("boost and mmr cannot be combined (not built)")
         return [d for d, _ in self.max_marginal_relevance_search_with_score_by_vector(
             embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, filter=filter,
             exact_filter=bool(kwargs.get("exact_filter", False)))]
@@ -1045,7 +1214,7 @@ class FAISS:
     def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
                                key: str = "book_id",
                                mmr: Optional[Tuple[int, float]] = None,
-                               distinct: Optional[str] = None, where=None
+                               distinct: Optional[str] = None, where=None, boost=None
                                ) -> List[List[Tuple[Document, float]]]:
         """The reference's per-student candidate path
         (candidate_builder.py:138-203) for many students in one device call.
@@ -1077,9 +1246,19 @@ class FAISS:
         grammar (``similarity_search_with_score_by_vector``; one dict: the same
         for all): the k nearest allowed documents that pass it, filtered on
         the device (``index.search_where`` over the means, with the same
-        exclusions).  Not together with ``mmr`` or ``distinct``."""
+        exclusions).  Not together with ``mmr`` or ``distinct``.
+
+        ``boost=[...]`` gives every profile a boost spec of the ``boost=``
+        grammar (one dict: the same for all), such as the student's reading
+        level: the k allowed documents with the best boosted score over the
+        whole store (``index.search_boost`` over the means, with the same
+        exclusions and, if given, the ``where`` predicates), where the
+        reference re-scores the ``k * 2`` nearest.  Not together with ``mmr``
+        or ``distinct``."""
         if distinct is not None and mmr is not None:
             raise ValueError("distinct and mmr cannot be combined")
+        if boost is not None and (mmr is not None or distinct is not None):
+            raise ValueError("boost cannot be combined with mmr or distinct (not built)")
         if where is not None and mmr is not None:
             raise ValueError("where and mmr cannot be combined")
         if where is not None and distinct is not None:
@@ -1088,6 +1267,9 @@ class FAISS:
         if where is not None and not isinstance(where, dict):
             where = list(where)
             _len_check_if_sized(profiles, where, "profiles", "where")
+        if boost is not None and not isinstance(boost, dict):
+            boost = list(boost)
+            _len_check_if_sized(profiles, boost, "profiles", "boost")
         if exclude is not None:
             exclude = list(exclude)
             _len_check_if_sized(profiles, exclude, "profiles", "exclude")
@@ -1095,7 +1277,15 @@ class FAISS:
         kept, rows, lists = self.profile_requests(profiles, exclude, key)
         if not kept:
             return out
-        if where is not None:
+        if boost is not None:
+            vec = self.index.mean_rows(rows)
+            if self._normalize_L2:
+                vfaiss.normalize_L2(vec)
+            scores, labels = self._search_boost(
+                vec, k, boost if isinstance(boost, dict) else [boost[p] for p in kept],
+                where=where if where is None or isinstance(where, dict)
+                else [where[p] for p in kept], exclude=lists)
+        elif where is not None:
             vec = self.index.mean_rows(rows)
             if self._normalize_L2:
                 vfaiss.normalize_L2(vec)

@@ -53,6 +53,9 @@ extern "C" {
 /* vs_search_where: skip the windows and answer every query with the
  * predicated scan. */
 #define VS_WHERE_SCAN 8
+/* vs_search_boost: skip the windows and answer every query with the boosted
+ * scan. */
+#define VS_BOOST_SCAN 16   /* skip the windows */
 
 /* Status codes. */
 #define VS_OK 0
@@ -438,6 +441,82 @@ int vs_where_plan(int64_t k, int metric, int raw, int64_t live, int64_t* out, in
  * scan, and the rows its streaming kernel loaded. */
 int vs_where_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int64_t* scanned,
                    int64_t* rows_streamed, int reset);
+
+/* ---- boosted searches ------------------------------------------------------
+ * Exact top-k under similarity plus a per-query function of the row's
+ * attributes (Qdrant's score boosting, Elasticsearch's function_score).  The
+ * reference adds a reading-level match, a staff-pick bonus and further soft
+ * terms to every candidate (src/recommendation_api/scoring.py:78-131), but only
+ * to the k * 2 rows a plain similarity search returned; these calls rank every
+ * row by the boosted score.
+ *
+ * For query q and live row r, with key the engine's key (-score for inner
+ * product, the squared distance for L2):
+ *   final_key(q, r) = fl32(key(q, r) - b(q, r))
+ * and the result is the k rows with the smallest (final_key, label), in that
+ * order (the lower label wins a tie, for both metrics).  D is -final_key
+ * (= fl32(score + b)) for inner product and final_key for L2, where it may be
+ * negative; padding is (-+FLT_MAX, -1).
+ *
+ * b(q, r) is float32, every operation rounded once to nearest, no FMA, the
+ * division correctly rounded.  Column c of the handle contributes by
+ * kinds[q][c] with params[q][c] = (t, s, w, miss) and the row's value v:
+ *   0 none: +0
+ *   1 near: w * max(0, 1 - |v - t| / s)
+ *   2 ramp: w * min(1, max(0, (v - t) / s))
+ * and `miss` when v is NaN and the kind is not 0 (max(0, x) is x > 0 ? x : +0,
+ * min(1, y) is y < 1 ? y : 1).  Tag term j < 4 adds tag_bonus[q][j] when
+ * (tags & tag_masks[q][j]) != 0, else +0.  b = (((c0 + c1) + c2) + c3) + g0 +
+ * g1 + g2 + g3, left to right.  The same sum over max(0, w, miss) /
+ * min(0, w, miss) of the columns whose kind is not 0 and max(0, bonus) /
+ * min(0, bonus) gives the per-query bounds U >= b >= L.
+ *
+ * vs_search_boost (scoring.py:78-131's reading-level and staff-pick terms over
+ * every row): kinds HOST int32 [n][ncol], params HOST [n][ncol][4] (ncol the
+ * handle's; all finite, s > 0, else VS_E_INVALID), tag_masks / tag_bonus HOST
+ * [n][4] or both NULL.  lo / hi / masks as vs_search_where (all NULL: no
+ * predicate) and excl_offs / excl_labels as vs_search_excl compose with the
+ * boost: a row that fails its predicate or is excluded is no candidate, the
+ * others are ranked by the final key.  Any k.
+ *
+ * Route A (windows): the queries are searched in raw order for a window of w
+ * entries (vs_where_plan's lengths for the raw order, at most 1,023), the
+ * window is re-ranked by final key, and a query is settled when its window
+ * reached the end of the rows or k entries were kept and final_key[k-1] <
+ * fl32(K_w - U), K_w the window's last raw key: every row outside has a raw key
+ * >= K_w and b <= U, so by monotone rounding a final key >= fl32(K_w - U).
+ * An unsettled query is searched again with a window four times longer, or
+ * sent to route B at once when its deficit exceeds the window's key spread.
+ * Route B (the boosted scan): the exact paged kernels with the boost, the
+ * predicate and the exclusion list applied where a row enters a query's list.
+ * VS_BOOST_SCAN sends every query there.  As for vs_search_where, a query's D
+ * bits may depend on the route, inside the engines' documented tolerance.
+ *
+ * Checked in vs_search_where's order: the index, the handle, n >= 0, k > 0 and
+ * k's bound; n == 0 is success; the boost arrays, the bounds, the exclusion
+ * offsets, the buffers.  A handle of another index or an older generation:
+ * VS_E_INVALID.  flags: VS_IN_DEVICE (x), VS_OUT_DEVICE (D, I), VS_BOOST_SCAN.
+ * The call reads a 4-byte count per round, so it waits for `stream`; a
+ * capturing stream: VS_E_UNSUPPORTED. */
+int vs_search_boost(vs_index* idx, const vs_attrs* attrs, const float* x, int64_t n, int64_t k,
+                    const int32_t* kinds, const float* params, const uint64_t* tag_masks,
+                    const float* tag_bonus, const float* lo, const float* hi,
+                    const uint64_t* masks, const int64_t* excl_offs, const int64_t* excl_labels,
+                    float* D, int64_t* I, int flags, void* stream);
+/* The definition of b on the host (scoring.py:78-131's soft terms as one
+ * function; touches no device): cols HOST [ncol][nrows], tags HOST [nrows] or
+ * NULL, the boost arrays of nq queries as above; b HOST [nq][nrows] =
+ * b(q, r), bit for bit what the kernels compute, bounds HOST [nq][2] = L, U. */
+int vs_boost_eval(int ncol, const float* cols, const uint64_t* tags, int64_t nrows,
+                  const int32_t* kinds, const float* params, const uint64_t* tag_masks,
+                  const float* tag_bonus, int64_t nq, float* b, float* bounds);
+/* Process-wide counters of the boosted searches (the searches that replace
+ * scoring.py:78-131's re-rank of k * 2 rows) since the last reset (reset != 0
+ * clears them): queries searched, window rounds run (summed over the calls'
+ * chunks), queries whose first window did not settle them, queries answered by
+ * the scan. */
+int vs_boost_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int64_t* scanned,
+                   int reset);
 
 /* ---- example searches ------------------------------------------------------
  * Recommendation from examples (Qdrant recommend, strategy="best_score"): the
