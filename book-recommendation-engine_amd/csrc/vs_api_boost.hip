@@ -19,28 +19,16 @@ const char* const kWhat = "vs_search_boost";
 // queries answered by the scan.
 std::atomic<int64_t> g_searches{0}, g_rounds{0}, g_requeried{0}, g_scanned{0};
 
-// What the chunks of one call share.
-struct BoostCall {
-  const vs_attrs* attrs = nullptr;
-  std::vector<WherePred> hp;  // the call's predicates, by query
-  std::vector<BoostSpec> hs;  // the call's boosts, by query
-  WherePred* dp = nullptr;
-  BoostSpec* ds = nullptr;
-  std::vector<int64_t> xoffs, xrows;  // the exclusion sets as rows in place (empty: none)
-  int64_t* dxoffs = nullptr;
-  int64_t* dxrows = nullptr;
-  bool scan_only = false;  // VS_BOOST_SCAN
-  bool excl() const { return !xrows.empty(); }
-};
-
 float boost_giveup() {
   const char* e = getenv("VS_BOOST_GIVEUP");
   return (float)(e ? atof(e) : kBoostGiveUp);
 }
 
+}  // namespace
+
 // The n specs of a call from its arrays; every parameter must be finite and
 // s > 0 (a column of kind 0 too), every bonus finite.
-int build_specs(const char* what, int ncol, const int32_t* kinds, const float* params,
+int vs::host::build_specs(const char* what, int ncol, const int32_t* kinds, const float* params,
                 const uint64_t* tag_masks, const float* tag_bonus, int64_t n,
                 std::vector<BoostSpec>* out) {
   if (ncol < 0 || ncol > kWhereMaxCols)
@@ -81,6 +69,8 @@ int build_specs(const char* what, int ncol, const int32_t* kinds, const float* p
   }
   return VS_OK;
 }
+
+namespace {
 
 // The windows of a boosted search: where_windows', while boost_rerank can sort
 // them (kBoostMaxWindow entries); *scan = what they leave goes to the scan.
@@ -284,7 +274,8 @@ int run_scan(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0,
 // decides whether the window was sufficient, and the rows of those queries are
 // written.  What the last window leaves unsettled, what the give-up rule sent
 // away, and what the call sent there at once is answered by route B.
-int run_boost(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0, hipStream_t st) {
+int run_boost_chunk(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0,
+                    hipStream_t st) {
   const int64_t live = idx->live();
   const WhereAttrs at = c.attrs->by_row();
   const WherePred* dp = c.dp + c0;
@@ -400,6 +391,11 @@ int run_boost(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0
 }
 
 }  // namespace
+
+int vs::host::run_boost(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0,
+                        hipStream_t st) {
+  return run_boost_chunk(idx, c, a, c0, st);
+}
 
 extern "C" {
 

@@ -18,18 +18,6 @@
 
 namespace vs {
 
-// b of row r in place: only the columns and the tag word the spec reads are loaded.
-__device__ __forceinline__ float boost_of_row(const BoostSpec& sp, const WhereAttrs& a,
-                                              int64_t r) {
-  float v[kWhereMaxCols];
-#pragma unroll
-  for (int c = 0; c < kWhereMaxCols; ++c)
-    v[c] = (c < a.ncol && sp.kind[c] != 0) ? a.cols[(int64_t)c * a.stride + r] : 0.0f;
-  const unsigned long long any = sp.mask[0] | sp.mask[1] | sp.mask[2] | sp.mask[3];
-  const unsigned long long t = (a.tags && any) ? a.tags[r] : 0ull;
-  return boost_value(sp, v, t);
-}
-
 // ---------------------------------------------------------------------------
 // Route A: one workgroup per slot s of a round's batch.  Din / Iin [ns][w] are
 // the raw entries as the engine wrote them with raw = 1 (ascending (key,

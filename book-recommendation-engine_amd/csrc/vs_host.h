@@ -675,6 +675,29 @@ int check_attrs(const char* what, const vs_index* idx, const vs_attrs* at);
 // 10M-row corpus that DESIGN.md section 7 "Boosted searches" describes has not
 // been run yet, so it is neither confirmed nor replaced.
 constexpr double kBoostGiveUp = 1.0;
+// What vs_api_boost.hip defines for vs_api_bonus.hip too.
+// What the chunks of one boosted call share.
+struct BoostCall {
+  const vs_attrs* attrs = nullptr;
+  std::vector<vs::WherePred> hp;  // the call's predicates, by query
+  std::vector<vs::BoostSpec> hs;  // the call's boosts, by query
+  vs::WherePred* dp = nullptr;
+  vs::BoostSpec* ds = nullptr;
+  std::vector<int64_t> xoffs, xrows;  // the exclusion sets as rows in place (empty: none)
+  int64_t* dxoffs = nullptr;
+  int64_t* dxrows = nullptr;
+  bool scan_only = false;  // VS_BOOST_SCAN
+  bool excl() const { return !xrows.empty(); }
+};
+// The n specs of a call from vs_search_boost's boost arrays, checked
+// ("<what>: ...").
+int build_specs(const char* what, int ncol, const int32_t* kinds, const float* params,
+                const uint64_t* tag_masks, const float* tag_bonus, int64_t n,
+                std::vector<vs::BoostSpec>* out);
+// One chunk of a boosted search (routes A and B) into a.D / a.I, in raw order
+// with labels = row + id_base; c0 = the chunk's first query in the call's
+// arrays.  Its queries and rounds count in vs_boost_stats.
+int run_boost(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0, hipStream_t st);
 
 }  // namespace host
 }  // namespace vs

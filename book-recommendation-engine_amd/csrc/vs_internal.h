@@ -865,4 +865,57 @@ hipError_t launch_gemm_topk_boost(int mode, const GemmWhereArgs& a, const BoostS
 hipError_t launch_gemv_topk_boost(int mode, int nq, const GemvWhereArgs& a,
                                   const BoostSpec* specs, Partials part, hipStream_t st);
 
+// Bonus searches (vs_bonus.hip; vs_api_bonus.hip vs_search_bonus): exact top-k
+// by final_key = fl32(fl32(key - b) - s), s a per-(query, row) number the
+// caller lists for at most kBonusMaxList rows per query.
+constexpr int kBonusMaxList = 1024;  // bonus_merge sorts a query's list in LDS
+// A chunk's lists: query q (0 .. nq - 1, the chunk's own numbering) lists the
+// rows in place rows[offs[q] .. offs[q + 1]) (ascending and distinct within a
+// query, every one a live row) with the bonuses vals[...]; e0 = offs[0] and
+// total = offs[nq] - offs[0] as the host knows them.
+struct BonusLists {
+  const int64_t* offs = nullptr;
+  const int64_t* rows = nullptr;
+  const float* vals = nullptr;
+  int64_t e0 = 0, total = 0;
+  int nq = 0;
+};
+// Entry e of the lists gets skey[e - e0] = the final key of its row for its query:
+// the rescoring's key (wave_dot's fp64 sum rounded once, exact_key<mode>; mode
+// IP, L2 or L2D; qn / xn the squared norms of MODE_L2), minus the query's boost
+// of the row (specs null: +0), minus the bonus; srow[e - e0] = the row, or -1 (and
+// key FLT_MAX) when the row fails the query's predicate (preds null: no
+// predicate; `at` is read only with preds or specs) or is in its exclusion
+// segment xrows[xoffs[q] .. xoffs[q + 1]) (both null: none).  preds, specs and
+// xoffs are indexed by the chunk's query.
+struct BonusScoreArgs {
+  int mode = MODE_IP;
+  const void* X = nullptr;
+  int esize = 4;
+  const float* xn = nullptr;
+  const float* Q = nullptr;
+  const float* qn = nullptr;
+  int64_t ld = 0;
+  BonusLists lists;
+  WhereAttrs at;
+  const WherePred* preds = nullptr;
+  const BoostSpec* specs = nullptr;
+  const int64_t* xoffs = nullptr;
+  const int64_t* xrows = nullptr;
+  float* skey = nullptr;
+  int64_t* srow = nullptr;
+};
+hipError_t launch_bonus_score(const BonusScoreArgs& a, hipStream_t st);
+// Query q's result: the first k of the two-way merge, by (final key, label), of
+// its base result Din / Iin ([nq][k], ascending (key, label) with D the key
+// (L2) or its negative (inner product), labels = row + id_base, -1 after the
+// end) without the entries whose row the query lists, and its scored list
+// entries (skey / srow as launch_bonus_score leaves them), into
+// row q of Dout / Iout ([nq][k], padded with the empty result of `mode`; not
+// Din / Iin).  *entered (optional) += the list entries written.
+hipError_t launch_bonus_merge(int mode, const float* Din, const int64_t* Iin, int k,
+                              const BonusLists& lists, const float* skey, const int64_t* srow,
+                              int64_t id_base, float* Dout, int64_t* Iout,
+                              unsigned long long* entered, hipStream_t st);
+
 }  // namespace vs

@@ -89,6 +89,9 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _c_int, _vp]),
     "vs_boost_eval": (_c_int, [_c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp]),
     "vs_boost_stats": (_c_int, [_i64p, _i64p, _i64p, _i64p, _c_int]),
+    "vs_search_bonus": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "vs_bonus_stats": (_c_int, [_i64p, _i64p, _i64p, _i64p, _c_int]),
     "vs_search_examples": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp,
                                     _vp, _vp, _c_int, _vp]),
     "vs_search_examples_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp,

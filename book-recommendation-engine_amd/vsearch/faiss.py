@@ -73,6 +73,8 @@ __all__ = [
     "profile_csr",
     "examples_csr",
     "examples_stats",
+    "bonus_csr",
+    "bonus_stats",
     "gather_picks",
     "normalize_L2",
     "read_index",
@@ -698,6 +700,84 @@ def boost_stats(reset: bool = False):
     return tuple(x.value for x in v)
 
 
+MAX_BONUS_LIST = 1024
+
+
+def bonus_csr(bonus, n: int):
+    """Per-query bonus lists as a CSR: ``(offs int64 (n + 1), labels int64,
+    values float32)``, checked as ``vs_search_bonus`` checks them.
+
+    ``bonus`` is ``None`` (n empty lists), a sequence of n entries — each a
+    mapping ``label -> value``, a pair ``(labels, values)`` or ``None`` — or an
+    ``(offs, labels, values)`` triple of arrays already in that form.  Every
+    value must be finite, the labels of one list distinct, and a list holds at
+    most ``MAX_BONUS_LIST`` entries; labels the index does not hold are
+    ignored by the search."""
+    n = int(n)
+    if bonus is None:
+        return (np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int64),
+                np.zeros(0, dtype=np.float32))
+    if (isinstance(bonus, tuple) and len(bonus) == 3
+            and all(isinstance(e, np.ndarray) and e.ndim == 1 for e in bonus)
+            and bonus[0].size == n + 1):
+        offs = np.ascontiguousarray(bonus[0], dtype=np.int64)
+        labels = np.ascontiguousarray(bonus[1], dtype=np.int64)
+        vals = np.ascontiguousarray(bonus[2], dtype=np.float32)
+        if (offs[0] != 0 or np.any(np.diff(offs) < 0) or offs[-1] != labels.size
+                or labels.size != vals.size):
+            raise ValueError("bonus: offsets must rise from 0 to len(labels) == len(values)")
+    else:
+        if isinstance(bonus, dict):
+            raise ValueError("bonus: one entry per query (a dict, a (labels, values) pair or None)")
+        entries = list(bonus)
+        if len(entries) != n:
+            raise ValueError(f"bonus: expected {n} lists, got {len(entries)}")
+        labs, vs = [], []
+        for e in entries:
+            if e is None:
+                l, v = (), ()
+            elif isinstance(e, dict):
+                l, v = list(e.keys()), list(e.values())
+            else:
+                if len(e) != 2:
+                    raise ValueError("bonus: a list is a dict, a (labels, values) pair or None")
+                l, v = e
+            l = np.asarray(l, dtype=np.int64).ravel()
+            v = np.asarray(v, dtype=np.float32).ravel()
+            if l.size != v.size:
+                raise ValueError("bonus: as many values as labels")
+            labs.append(l)
+            vs.append(v)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            np.cumsum([l.size for l in labs], out=offs[1:])
+        labels = np.ascontiguousarray(np.concatenate(labs) if n and offs[-1] else
+                                      np.zeros(0, dtype=np.int64), dtype=np.int64)
+        vals = np.ascontiguousarray(np.concatenate(vs) if n and offs[-1] else
+                                    np.zeros(0, dtype=np.float32), dtype=np.float32)
+    if not np.isfinite(vals).all():
+        raise ValueError("bonus: a value that is not finite")
+    if labels.size > 1:  # one sort by (query, label) for every list
+        qs = np.repeat(np.arange(n, dtype=np.int64), np.diff(offs))
+        order = np.lexsort((labels, qs))
+        ls, qs = labels[order], qs[order]
+        if np.any((ls[1:] == ls[:-1]) & (qs[1:] == qs[:-1])):
+            raise ValueError("bonus: a label twice in one list")
+    if n and np.diff(offs).max() > MAX_BONUS_LIST:
+        raise ValueError(f"bonus: a list longer than {MAX_BONUS_LIST} entries")
+    return offs, labels, vals
+
+
+def bonus_stats(reset: bool = False):
+    """(queries searched, listed live rows scored, queries whose base search
+    carried an extra exclusion, result entries that are listed rows) of the
+    bonus searches of this process since the last reset."""
+    v = [ctypes.c_int64(0) for _ in range(4)]
+    _lib.check(_lib.load().vs_bonus_stats(*[ctypes.byref(x) for x in v], 1 if reset else 0),
+               "vs_bonus_stats")
+    return tuple(x.value for x in v)
+
+
 class Index:
     """Common base (faiss.Index)."""
 
@@ -1083,6 +1163,65 @@ class IndexFlat(Index):
             _ptr(hi) if hi is not None else None, _ptr(masks) if masks is not None else None,
             None, None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags,
             ctypes.c_void_p(stream)), "vs_search_boost")
+
+    def _bonus_call(self, x_ptr, n, k, bonus, attrs, boost, where, exclude, D_ptr, I_ptr, flags,
+                    stream):
+        if attrs is None:
+            if boost is not None or where is not None:
+                raise ValueError("search_bonus: boost= and where= need attrs=")
+            kinds = params = tmasks = tbonus = lo = hi = masks = None
+        else:
+            if attrs.index is not self:
+                raise ValueError("the Attributes belong to another index")
+            kinds, params, tmasks, tbonus = boost_arrays(boost, attrs.ncol, n)
+            lo, hi, masks = (None, None, None) if where is None else \
+                where_arrays(where, attrs.ncol, n)
+        boffs, blabels, bvals = bonus_csr(bonus, n)
+        offs, labels = (None, None) if exclude is None else exclusion_csr(exclude, n)
+
+        def p(a):
+            return _ptr(a) if a is not None else None
+
+        _lib.check(self._lib.vs_search_bonus(
+            self._h, attrs._h if attrs is not None else None, x_ptr, n, k,
+            boffs.ctypes.data, p(blabels), p(bvals), p(kinds), p(params), p(tmasks), p(tbonus),
+            p(lo), p(hi), p(masks), offs.ctypes.data if offs is not None else None, p(labels),
+            D_ptr, I_ptr, flags, stream), "vs_search_bonus")
+
+    def search_bonus(self, x, k, bonus, *, attrs: Attributes | None = None, boost=None, where=None,
+                     exclude=None, scan: bool = False):
+        """The k rows with the best score after per-query, per-row bonuses,
+        exactly: ``bonus`` lists per query up to 1,024 ``(label, s)`` pairs
+        (``bonus_csr``), and every allowed row is ranked by
+        ``fl32(fl32(key - b) - s)``, s = 0 for a row the query does not list,
+        key and b as in ``search_boost`` (b = 0 without ``attrs``), ties to the
+        lower label.  D is ``score + b + s`` for inner product and
+        ``distance - b - s`` for L2.  ``boost`` and ``where`` need ``attrs``
+        (``index.attributes``); ``exclude`` as in ``search``.  A listed row
+        that fails its predicate or is excluded is not returned.  Without any
+        list the answer is ``search_boost``'s (with ``attrs``) or
+        ``search(raw=True)``'s, bit for bit."""
+        x = _as_f32_rows(x)
+        n, d = x.shape
+        assert d == self._d
+        k = int(k)
+        assert k > 0
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        self._bonus_call(_ptr(x), n, k, bonus, attrs, boost, where, exclude, _ptr(D), _ptr(I),
+                         _lib.BOOST_SCAN if scan else 0, None)
+        return D, I
+
+    def search_bonus_device(self, xq_ptr: int, n: int, k: int, bonus, D_ptr: int, I_ptr: int,
+                            stream: int = 0, attrs: Attributes | None = None, boost=None,
+                            where=None, exclude=None, scan: bool = False) -> None:
+        """``search_bonus`` with the queries and the results on this index's
+        device, on `stream` (the call waits for the stream; a capturing stream
+        is refused).  The lists, boosts and predicates stay host arrays."""
+        flags = _lib.IN_DEVICE | _lib.OUT_DEVICE | (_lib.BOOST_SCAN if scan else 0)
+        self._bonus_call(ctypes.c_void_p(xq_ptr), int(n), int(k), bonus, attrs, boost, where,
+                         exclude, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), flags,
+                         ctypes.c_void_p(stream))
 
     def _examples_args(self, positive, negative):
         poffs, plab, pvec = examples_csr(positive, None, self._d)

@@ -41,6 +41,11 @@ types and error behaviour:
   documents' metadata (reading-level match, staff pick), ranked over every
   document on the device (``index.search_boost``), where the reference adds
   those terms to the ``k * 2`` nearest only (scoring.py:78-131).
+* ``bonus=`` (library-specific) — a number per (query, ``metadata[bonus_key]``
+  value) added to the score of every document with that value, ranked over
+  every document on the device (``index.search_bonus``): the reference's
+  social and recency terms (scoring.py:116-125), which are numbers per
+  (student, book) and not functions of a book's metadata.
 """
 
 from __future__ import annotations
@@ -861,7 +866,13 @@ class FAISS:
         boost specs (one dict for every query or one per query), composed with
         ``where`` predicates and exclusion lists.  One attribute handle serves
         the fields of both grammars."""
-        n = vec.shape[0]
+        attrs, specs, preds = self._boost_args(vec.shape[0], boost, where)
+        return self.index.search_boost(vec, k, attrs, specs, where=preds, exclude=exclude)
+
+    def _boost_args(self, n: int, boost, where):
+        """What ``index.search_boost`` / ``index.search_bonus`` take for the
+        grammar's boost specs and ``where`` predicates of n queries: (attribute
+        handle, boost specs, predicates or None)."""
         specs = [boost] * n if boost is None or isinstance(boost, dict) else list(boost)
         if len(specs) != n:
             raise ValueError(f"boost: {len(specs)} specs for {n} queries")
@@ -879,10 +890,49 @@ class FAISS:
             raise ValueError(f"boost and where: more than {WHERE_MAX_PAIRS} (field, value) pairs "
                              "together")
         attrs = self._where_attributes(nums, pairs)
-        return self.index.search_boost(
-            vec, k, attrs, [boost_spec(sp, nums, pairs, self._where_is_numeric) for sp in specs],
-            where=None if where is None else [where_predicate(p, nums, pairs) for p in preds],
-            exclude=exclude)
+        return (attrs, [boost_spec(sp, nums, pairs, self._where_is_numeric) for sp in specs],
+                None if where is None else [where_predicate(p, nums, pairs) for p in preds])
+
+    def _bonus_lists(self, bonus, n: int, bonus_key: str) -> List[Dict[int, float]]:
+        """``bonus=`` of n queries as ``index.search_bonus`` takes it: one dict
+        ``metadata[bonus_key] value -> number`` for every query or a sequence of
+        n of them (``None``: no bonus) becomes one dict ``label -> number`` per
+        query.  Every stored row with a value gets its number (a re-embedded
+        book's rows all do); values the store does not hold are ignored."""
+        entries = [bonus] * n if bonus is None or isinstance(bonus, dict) else list(bonus)
+        if len(entries) != n:
+            raise ValueError(f"bonus: {len(entries)} lists for {n} queries")
+        table = self._key_labels(bonus_key)
+        out = []
+        for e in entries:
+            lists: Dict[int, float] = {}
+            if e is not None:
+                if not isinstance(e, dict):
+                    raise ValueError(f"bonus: a dict from {bonus_key} values to numbers "
+                                     "(or None) per query")
+                for value, s in e.items():
+                    if not _is_number(s) or not math.isfinite(s):
+                        raise ValueError(f"bonus: {value!r} needs a finite number")
+                    for label in table.get(value, ()):
+                        lists[label] = float(s)
+            if len(lists) > vfaiss.MAX_BONUS_LIST:
+                raise ValueError(f"bonus: more than {vfaiss.MAX_BONUS_LIST} documents in one "
+                                 "query's list")
+            out.append(lists)
+        return out
+
+    def _search_bonus(self, vec, k: int, bonus, bonus_key: str = "book_id", boost=None,
+                      where=None, exclude=None):
+        """``index.search_bonus`` of the queries `vec`: the ``bonus=`` lists
+        composed with the grammar's boost specs, ``where`` predicates and
+        exclusion lists."""
+        n = vec.shape[0]
+        lists = self._bonus_lists(bonus, n, bonus_key)
+        if boost is None and where is None:
+            return self.index.search_bonus(vec, k, lists, exclude=exclude)
+        attrs, specs, preds = self._boost_args(n, boost, where)
+        return self.index.search_bonus(vec, k, lists, attrs=attrs, boost=specs, where=preds,
+                                       exclude=exclude)
 
     # -- reads ------------------------------------------------------------------------------
     def similarity_search_with_score_by_vector(self, embedding: List[float], k: int = 4,
@@ -928,6 +978,17 @@ class FAISS:
         returned scores are the boosted ones (score + boost for an
         inner-product store, distance - boost for an L2 store).  Combines with
         ``where`` and ``exclude_ids``; with ``distinct``, `filter` or MMR it is
+        a ValueError (library-specific).
+
+        ``bonus={value: number, ...}`` with ``bonus_key="book_id"``: every
+        document whose ``metadata[bonus_key]`` is a listed value has the number
+        added to its score (subtracted from its distance in an L2 store)
+        before the ranking, over every document on the device
+        (``index.search_bonus``): a book two neighbours just borrowed can
+        enter the result from anywhere in the store, and a negative number
+        demotes one.  Values the store does not hold are ignored.  The
+        returned scores are the final ones.  Combines with ``where``,
+        ``boost`` and ``exclude_ids``; with ``distinct``, `filter` or MMR it is
         a ValueError (library-specific)."""
         vector = np.array([embedding], dtype=np.float32)
         if self._normalize_L2:
@@ -945,13 +1006,21 @@ class FAISS:
         if boost is not None and (distinct is not None or filter is not None or exact_filter):
             raise ValueError("boost cannot be combined with distinct or filter (not built); "
                              "where= and exclude_ids compose with it")
+        bonus = kwargs.get("bonus")
+        if bonus is not None and (distinct is not None or filter is not None or exact_filter):
+            raise ValueError("bonus cannot be combined with distinct or filter (not built); "
+                             "where=, boost= and exclude_ids compose with it")
         drop = None
         if exclude_ids is not None:
             if exact_filter and filter is not None:
                 raise ValueError("exclude_ids and exact_filter cannot be combined")
             wanted = set(exclude_ids)
             drop = [i for i, id_ in self.index_to_docstore_id.items() if id_ in wanted]
-        if boost is not None:
+        if bonus is not None:
+            scores, indices = self._search_bonus(
+                vector, k, [bonus], kwargs.get("bonus_key", "book_id"), boost=boost, where=where,
+                exclude=None if drop is None else [drop])
+        elif boost is not None:
             scores, indices = self._search_boost(vector, k, boost, where=where,
                                                  exclude=None if drop is None else [drop])
         elif distinct is not None:
@@ -1049,13 +1118,16 @@ class FAISS:
 
     def similarity_search_batch_by_vector(self, embeddings, k: int = 4,
                                           distinct: Optional[str] = None, where=None,
-                                          boost=None):
+                                          boost=None, bonus=None, bonus_key: str = "book_id"):
         """Batched variant (one engine call for many queries): list of
         [(Document, score)] per query, label -1 skipped.  ``distinct`` as in
         ``similarity_search_with_score_by_vector``; ``where``: one predicate of
         its grammar per query (or one dict for all of them), not together with
         ``distinct``; ``boost``: one boost spec per query (or one dict for all
-        of them), with ``where`` or alone, not together with ``distinct``."""
+        of them), with ``where`` or alone, not together with ``distinct``;
+        ``bonus``: one ``{bonus_key value: number}`` dict per query (or one
+        dict for all of them), with ``where`` and ``boost`` or alone, not
+        together with ``distinct``."""
         vec = np.array(embeddings, dtype=np.float32)
         if self._normalize_L2:
             vfaiss.normalize_L2(vec)
@@ -1063,7 +1135,12 @@ class FAISS:
             raise ValueError("where and distinct cannot be combined")
         if boost is not None and distinct is not None:
             raise ValueError("boost and distinct cannot be combined (not built)")
-        if boost is not None:
+        if bonus is not None and distinct is not None:
+            raise ValueError("bonus and distinct cannot be combined (not built)")
+        if bonus is not None:
+            scores, indices = self._search_bonus(vec, k, bonus, bonus_key, boost=boost,
+                                                 where=where)
+        elif boost is not None:
             scores, indices = self._search_boost(vec, k, boost, where=where)
         elif where is not None:
             scores, indices = self._search_where(vec, k, where)
@@ -1138,6 +1215,8 @@ class FAISS:
             raise ValueError("where and mmr cannot be combined")
         if kwargs.get("boost") is not None:
             raise ValueError("boost and mmr cannot be combined (not built)")
+        if kwargs.get("bonus") is not None:
+            raise ValueError("bonus and mmr cannot be combined (not built)")
         return [d for d, _ in self.max_marginal_relevance_search_with_score_by_vector(
             embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, filter=filter,
             exact_filter=bool(kwargs.get("exact_filter", False)))]
@@ -1214,7 +1293,8 @@ class FAISS:
     def recommend_for_profiles(self, profiles, k: int = 4, *, exclude=None,
                                key: str = "book_id",
                                mmr: Optional[Tuple[int, float]] = None,
-                               distinct: Optional[str] = None, where=None, boost=None
+                               distinct: Optional[str] = None, where=None, boost=None,
+                               bonus=None, bonus_key: str = "book_id"
                                ) -> List[List[Tuple[Document, float]]]:
         """The reference's per-student candidate path
         (candidate_builder.py:138-203) for many students in one device call.
@@ -1254,11 +1334,21 @@ class FAISS:
         whole store (``index.search_boost`` over the means, with the same
         exclusions and, if given, the ``where`` predicates), where the
         reference re-scores the ``k * 2`` nearest.  Not together with ``mmr``
-        or ``distinct``."""
+        or ``distinct``.
+
+        ``bonus=[...]`` gives every profile a dict ``metadata[bonus_key] value
+        -> number`` (one dict: the same for all), such as
+        ``students.neighbour_bonus``'s social term: the number is added to the
+        score of every document with that value before the ranking over the
+        whole store (``index.search_bonus`` over the means, with the same
+        exclusions and, if given, the ``where`` predicates and ``boost``
+        specs).  Not together with ``mmr`` or ``distinct``."""
         if distinct is not None and mmr is not None:
             raise ValueError("distinct and mmr cannot be combined")
         if boost is not None and (mmr is not None or distinct is not None):
             raise ValueError("boost cannot be combined with mmr or distinct (not built)")
+        if bonus is not None and (mmr is not None or distinct is not None):
+            raise ValueError("bonus cannot be combined with mmr or distinct (not built)")
         if where is not None and mmr is not None:
             raise ValueError("where and mmr cannot be combined")
         if where is not None and distinct is not None:
@@ -1270,6 +1360,9 @@ class FAISS:
         if boost is not None and not isinstance(boost, dict):
             boost = list(boost)
             _len_check_if_sized(profiles, boost, "profiles", "boost")
+        if bonus is not None and not isinstance(bonus, dict):
+            bonus = list(bonus)
+            _len_check_if_sized(profiles, bonus, "profiles", "bonus")
         if exclude is not None:
             exclude = list(exclude)
             _len_check_if_sized(profiles, exclude, "profiles", "exclude")
@@ -1277,7 +1370,17 @@ class FAISS:
         kept, rows, lists = self.profile_requests(profiles, exclude, key)
         if not kept:
             return out
-        if boost is not None:
+        if bonus is not None:
+            vec = self.index.mean_rows(rows)
+            if self._normalize_L2:
+                vfaiss.normalize_L2(vec)
+            scores, labels = self._search_bonus(
+                vec, k, bonus if isinstance(bonus, dict) else [bonus[p] for p in kept], bonus_key,
+                boost=boost if boost is None or isinstance(boost, dict)
+                else [boost[p] for p in kept],
+                where=where if where is None or isinstance(where, dict)
+                else [where[p] for p in kept], exclude=lists)
+        elif boost is not None:
             vec = self.index.mean_rows(rows)
             if self._normalize_L2:
                 vfaiss.normalize_L2(vec)

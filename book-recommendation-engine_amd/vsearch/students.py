@@ -248,3 +248,42 @@ def student_neighbours_of(student: str, keys: Sequence[str], vectors, *, k: int 
     if index is None:
         index = StudentIndex(keys, vectors, quantize=quantize, device=device)
     return index.neighbours_of(student, k)
+
+
+def neighbour_bonus(neighbours, checkouts, weight: float = 0.2, top: int = 5):
+    """The social term of the reference's ranking formula (scoring.py:116-119,
+    ``social_boost_weight * neighbour_recent``) as the ``bonus=`` lists of
+    ``FAISS.recommend_for_profiles``: ``{a: {book_id: float32(weight) *
+    float32(count)}}``.
+
+    ``neighbours`` are ``(a, b, sim)`` rows as ``student_neighbours`` /
+    ``StudentIndex.neighbours`` return them; per student a the ``top`` rows of
+    the greatest sim are kept (candidate_builder.py:395's ``ORDER BY sim DESC
+    LIMIT 5``; an equal sim keeps the earlier row).  ``checkouts`` are
+    ``(student, book_id)`` rows the caller has already cut to its recency
+    window; ``count`` is the number of those rows whose student is one of a's
+    kept neighbours, a repeated row counted again (the loop at
+    candidate_builder.py:410-412).  A student none of whose neighbours checked
+    anything out has no entry.  Plain host code: a sort of a few rows per
+    student."""
+    rows_of = {}
+    for a, b, sim in neighbours:
+        rows_of.setdefault(a, []).append((float(sim), b))
+    books_of = {}
+    for student, book in checkouts:
+        books_of.setdefault(student, []).append(book)
+    w = np.float32(weight)
+    out = {}
+    for a, rows in rows_of.items():
+        order = sorted(range(len(rows)), key=lambda i: -rows[i][0])  # stable: ties keep their order
+        kept = []
+        for i in order[:int(top)]:
+            if rows[i][1] not in kept:
+                kept.append(rows[i][1])
+        counts = {}
+        for b in kept:
+            for book in books_of.get(b, ()):
+                counts[book] = counts.get(book, 0) + 1
+        if counts:
+            out[a] = {book: w * np.float32(c) for book, c in counts.items()}
+    return out

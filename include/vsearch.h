@@ -518,6 +518,69 @@ int vs_boost_eval(int ncol, const float* cols, const uint64_t* tags, int64_t nro
 int vs_boost_stats(int64_t* searches, int64_t* rounds, int64_t* requeried, int64_t* scanned,
                    int reset);
 
+/* ---- bonus searches ----------------------------------------------------------
+ * Exact top-k under per-query, per-row score bonuses: the terms of the
+ * reference's ranking formula that are numbers per (student, book) and not
+ * functions of a book's attributes (scoring.py:116-125: the social term
+ * gamma * neighbour_recent and the recency term), applied to every row instead
+ * of to the k * 2 rows a plain search returned.
+ *
+ * Query q lists at most 1,024 pairs (label, s): bonus_offs HOST int64 [n + 1]
+ * from 0, bonus_labels HOST [bonus_offs[n]], bonus_vals HOST float
+ * [bonus_offs[n]].  Every s is finite and the labels of one list are distinct;
+ * their order does not matter.  Labels that are not live labels of the index
+ * (and -1) are ignored, as in vs_search_excl.  With key and b(q, r) as for
+ * vs_search_boost (b = +0 when attrs is NULL),
+ *   final_key = fl32(fl32(key - b) - s)   for a row q lists,
+ *   final_key =      fl32(key - b)        otherwise,
+ * two separately rounded subtractions, never contracted; a positive s improves
+ * a row under both metrics and s = +0 changes nothing.  The result is the k
+ * allowed rows (live, passing q's predicate, not in q's exclusion list) with
+ * the smallest (final_key, label), the lower label first among equal keys
+ * under both metrics; D is -final_key for inner product and final_key for L2,
+ * padded with (-+FLT_MAX, -1).  A listed row that fails the predicate or is
+ * excluded is no candidate, whatever its bonus.  Any k.
+ *
+ * attrs may be NULL: kinds, params, tag_masks, tag_bonus, lo, hi and masks must
+ * then be NULL too (else VS_E_INVALID) and the base search is the plain search
+ * in raw order (vs_search with VS_RAW_ORDER, vs_search_excl with lists).  With
+ * a handle the arrays are exactly vs_search_boost's and the base search is
+ * that call's (VS_BOOST_SCAN is passed through to it).  bonus_offs NULL or all
+ * lists empty: the base search's answer bit for bit.
+ *
+ * Route: the base search ranks the allowed rows without the listed rows of
+ * negative s (they join the query's exclusion segment; -0 counts as not
+ * negative) by their bonus-free keys; every listed live row is scored directly;
+ * the two sets are merged by (final_key, label).  An unlisted row of the true
+ * top-k is in the base result, because every row that beats it in the
+ * bonus-free order over that set also beats it in the final order (rounded
+ * subtraction is monotone: fl32(x - s) <= x for s >= 0).  A listed row always
+ * carries the rescoring's key (the fp64 sum rounded once, then the metric's
+ * formula); an unlisted row carries the key of the base search's route, so, as
+ * for vs_search_boost, a query's D bits may depend on the base route, inside
+ * the engines' documented tolerance.
+ *
+ * Checked in vs_search_boost's order: the index, n >= 0, k > 0 and k's bound;
+ * n == 0 is success; the boost arrays; the bonus lists (offsets that do not
+ * start at 0 or decrease, a value that is not finite, a label twice in one
+ * list: VS_E_INVALID; a list longer than 1,024: VS_E_UNSUPPORTED); the bounds,
+ * the exclusion offsets, the buffers, the handle.  flags: VS_IN_DEVICE (x),
+ * VS_OUT_DEVICE (D, I), VS_BOOST_SCAN.  The call waits for `stream`; a
+ * capturing stream: VS_E_UNSUPPORTED. */
+int vs_search_bonus(vs_index* idx, const vs_attrs* attrs, const float* x, int64_t n, int64_t k,
+                    const int64_t* bonus_offs, const int64_t* bonus_labels,
+                    const float* bonus_vals, const int32_t* kinds, const float* params,
+                    const uint64_t* tag_masks, const float* tag_bonus, const float* lo,
+                    const float* hi, const uint64_t* masks, const int64_t* excl_offs,
+                    const int64_t* excl_labels, float* D, int64_t* I, int flags, void* stream);
+/* Process-wide counters of the bonus searches since the last reset (reset != 0
+ * clears them): queries searched, listed live rows scored, queries whose base
+ * search carried at least one extra exclusion (a listed live row of negative
+ * s), result entries that are listed rows.  With a handle the base searches
+ * count in vs_boost_stats as well. */
+int vs_bonus_stats(int64_t* searches, int64_t* listed, int64_t* demoted, int64_t* entered,
+                   int reset);
+
 /* ---- example searches ------------------------------------------------------
  * Recommendation from examples (Qdrant recommend, strategy="best_score"): the
  * rows nearest to ANY liked example that no disliked example is at least as
