@@ -1,7 +1,8 @@
 // vs_api_bonus.hip — bonus searches (DESIGN.md "Bonus searches"):
 // vs_search_bonus, vs_bonus_stats.  The base search is the boosted search's
-// chunk (run_boost) with an attribute handle and the plain raw-order search
-// without one; the listed rows are scored and merged by vs_bonus.hip.
+// chunk (run_where on a boosted call) with an attribute handle and the plain
+// raw-order search without one; the listed rows are scored and merged by
+// vs_bonus.hip.
 #include <atomic>
 
 #include "vs_host.h"
@@ -33,7 +34,7 @@ struct BonusCall {
   std::vector<int64_t> xoffs, xrows;
   int64_t* dxoffs = nullptr;
   int64_t* dxrows = nullptr;
-  BoostCall base;
+  WhereCall base;  // a boosted call; without attributes only its exclusion sets are used
   unsigned long long* dentered = nullptr;
   bool any() const { return !rows.empty(); }
   bool excl() const { return !xrows.empty(); }
@@ -117,7 +118,7 @@ void build_lists(const vs_index* idx, int64_t n, const int64_t* offs, const int6
 
 // The base search of one chunk into b.D / b.I: raw order, labels = row + id_base.
 int run_base(vs_index* idx, const BonusCall& c, const SearchArgs& b, int64_t c0, hipStream_t st) {
-  if (c.base.attrs) return run_boost(idx, c.base, b, c0, st);
+  if (c.base.attrs) return run_where(idx, c.base, b, c0, st);
   if (c.base.excl())
     return run_excluded_chunk(idx, b, c.base.xoffs.data() + c0, c.base.dxoffs + c0, c.base.dxrows,
                               st);
@@ -236,6 +237,7 @@ int vs_search_bonus(vs_index* idx, const vs_attrs* attrs, const float* x, int64_
   Scratch scr(st);
   c.base.attrs = attrs;
   c.base.scan_only = (flags & VS_BOOST_SCAN) != 0;
+  c.base.stats = &g_boost_stats;
   const bool empty = idx->ntotal == 0 || idx->live() == 0;
   int64_t demoted = 0;
   if (!empty) {
@@ -247,23 +249,9 @@ int vs_search_bonus(vs_index* idx, const vs_attrs* attrs, const float* x, int64_
       c.base.xoffs = c.xoffs;
       c.base.xrows = c.xrows;
     }
-    if (attrs) {
-      build_preds(lo, hi, masks, n, attrs->ncol, &c.base.hp);
-      rc = upload(scr, c.base.hp.data(), c.base.hp.size() * sizeof(WherePred), (void**)&c.base.dp,
-                  st, kWhat);
-      if (!rc)
-        rc = upload(scr, c.base.hs.data(), c.base.hs.size() * sizeof(BoostSpec),
-                    (void**)&c.base.ds, st, kWhat);
-      if (rc) return rc;
-    }
-    if (c.base.excl()) {
-      rc = upload(scr, c.base.xoffs.data(), c.base.xoffs.size() * sizeof(int64_t),
-                  (void**)&c.base.dxoffs, st, kWhat);
-      if (!rc)
-        rc = upload(scr, c.base.xrows.data(), c.base.xrows.size() * sizeof(int64_t),
-                    (void**)&c.base.dxrows, st, kWhat);
-      if (rc) return rc;
-    }
+    if (attrs) build_preds(lo, hi, masks, n, attrs->ncol, &c.base.hp);
+    rc = upload_call(kWhat, scr, &c.base, st);
+    if (rc) return rc;
     if (c.any()) {
       rc = upload(scr, c.offs.data(), c.offs.size() * sizeof(int64_t), (void**)&c.doffs, st, kWhat);
       if (!rc)

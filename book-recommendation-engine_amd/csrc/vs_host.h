@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -642,8 +643,8 @@ inline int where_windows(int64_t need, int64_t live, int64_t* out, int nmax, boo
   }
   return n;
 }
-// What vs_api_where.hip defines for vs_api_boost.hip too (`what`: the entry
-// point's name, the prefix of every message).
+// What vs_api_where.hip defines for the boosted and the bonus searches too
+// (`what`: the entry point's name, the prefix of every message).
 // A NaN in lo / hi ([n][ncol], either may be null) is VS_E_INVALID.
 int check_bounds(const char* what, const float* lo, const float* hi, int64_t n, int ncol);
 // The n predicates of a call's where arrays (all null: every live row passes).
@@ -651,7 +652,7 @@ void build_preds(const float* lo, const float* hi, const uint64_t* masks, int64_
                  std::vector<vs::WherePred>* out);
 // The staged queries list[0 .. cnt) (device) of chunk `a` as a batch of their own.
 int gather_batch(const vs_index* idx, const SearchArgs& a, const int* list, int cnt, Scratch& scr,
-                 SearchArgs* b, hipStream_t st, const char* what = "vs_search_where");
+                 SearchArgs* b, hipStream_t st, const char* what);
 // The exclusion sets (CSR xoffs / xrows by the call's query) of the chunk's
 // queries `list` (c0: the chunk's first query) as a CSR by slot.
 void slot_excl(const std::vector<int64_t>& xoffs, const std::vector<int64_t>& xrows, int64_t c0,
@@ -660,10 +661,53 @@ void slot_excl(const std::vector<int64_t>& xoffs, const std::vector<int64_t>& xr
 // *dst = scratch holding the `bytes` at src (copied on `st`; src must live
 // until the stream has passed the copy).
 int upload(Scratch& scr, const void* src, size_t bytes, void** dst, hipStream_t st,
-           const char* what = "vs_search_where");
+           const char* what);
 // The checks of an attribute handle against its index (foreign, stale); the
 // caller holds the reader lock.
 int check_attrs(const char* what, const vs_index* idx, const vs_attrs* at);
+
+// The counters of one kind of search on the route driver (vs_where_stats,
+// vs_boost_stats): queries searched, window rounds run (summed over chunks),
+// queries searched again after their first window, queries answered by the
+// scan, rows the where scan's streaming kernel loaded (the boosted scan counts
+// none).
+struct RouteStats {
+  std::atomic<int64_t> searches{0}, rounds{0}, requeried{0}, scanned{0}, streamed{0};
+  void reset() { searches = 0, rounds = 0, requeried = 0, scanned = 0, streamed = 0; }
+};
+// What the chunks of one where or boosted call share.  Specs given (hs / ds):
+// a boosted call, whose chunks arrive in raw order.
+struct WhereCall {
+  const vs_attrs* attrs = nullptr;
+  std::vector<vs::WherePred> hp;  // the call's predicates, by query
+  std::vector<vs::BoostSpec> hs;  // the call's boosts, by query (empty: a where call)
+  vs::WherePred* dp = nullptr;
+  vs::BoostSpec* ds = nullptr;
+  std::vector<int64_t> xoffs, xrows;  // the exclusion sets as rows in place (empty: none)
+  int64_t* dxoffs = nullptr;
+  int64_t* dxrows = nullptr;
+  bool scan_only = false;    // VS_WHERE_SCAN / VS_BOOST_SCAN
+  bool count_first = false;  // a small where call: count, then choose the route per query
+  RouteStats* stats = nullptr;  // the kind's counters
+  bool excl() const { return !xrows.empty(); }
+  bool boosted() const { return !hs.empty(); }
+};
+// The device copies of the call's predicates (where it has any), boosts and
+// exclusion sets into `scr`; the vectors must live until `st` has passed them.
+int upload_call(const char* what, Scratch& scr, WhereCall* c, hipStream_t st);
+// One chunk of a where or boosted search into a.D / a.I (labels = row +
+// id_base; c0 = the chunk's first query in the call's arrays): the window
+// rounds of route A, then the predicated scan (route B) for what they leave.
+// Its messages name vs_search_where or vs_search_boost by the call's kind.
+int run_where(vs_index* idx, const WhereCall& c, const SearchArgs& a, int64_t c0, hipStream_t st);
+// vs_search_where / vs_search_boost after the checks of their own arguments
+// (idx, attrs, n > 0, k, the boosts): the checks of the where arrays, the
+// exclusion lists and the buffers, the lock, the device, the uploads and the
+// chunks.  c: attrs, hs, scan_only, count_first and stats set.
+int search_where_call(const char* what, vs_index* idx, WhereCall* c, const float* x, int64_t n,
+                      int64_t k, const float* lo, const float* hi, const uint64_t* masks,
+                      const int64_t* excl_offs, const int64_t* excl_labels, float* D, int64_t* I,
+                      int flags, hipStream_t st);
 
 // ---- boosted searches (vs_api_boost.hip) ---------------------------------------
 // The give-up rule of route A: after a round, a query whose deficit
@@ -675,29 +719,17 @@ int check_attrs(const char* what, const vs_index* idx, const vs_attrs* at);
 // 10M-row corpus that DESIGN.md section 7 "Boosted searches" describes has not
 // been run yet, so it is neither confirmed nor replaced.
 constexpr double kBoostGiveUp = 1.0;
-// What vs_api_boost.hip defines for vs_api_bonus.hip too.
-// What the chunks of one boosted call share.
-struct BoostCall {
-  const vs_attrs* attrs = nullptr;
-  std::vector<vs::WherePred> hp;  // the call's predicates, by query
-  std::vector<vs::BoostSpec> hs;  // the call's boosts, by query
-  vs::WherePred* dp = nullptr;
-  vs::BoostSpec* ds = nullptr;
-  std::vector<int64_t> xoffs, xrows;  // the exclusion sets as rows in place (empty: none)
-  int64_t* dxoffs = nullptr;
-  int64_t* dxrows = nullptr;
-  bool scan_only = false;  // VS_BOOST_SCAN
-  bool excl() const { return !xrows.empty(); }
-};
+float boost_giveup();
+// The windows of a boosted search: where_windows', while boost_rerank can sort
+// them (kBoostMaxWindow entries); *scan = what they leave goes to the scan.
+int boost_windows(int64_t k, int64_t live, int64_t* out, int nmax, bool* scan);
 // The n specs of a call from vs_search_boost's boost arrays, checked
 // ("<what>: ...").
 int build_specs(const char* what, int ncol, const int32_t* kinds, const float* params,
                 const uint64_t* tag_masks, const float* tag_bonus, int64_t n,
                 std::vector<vs::BoostSpec>* out);
-// One chunk of a boosted search (routes A and B) into a.D / a.I, in raw order
-// with labels = row + id_base; c0 = the chunk's first query in the call's
-// arrays.  Its queries and rounds count in vs_boost_stats.
-int run_boost(vs_index* idx, const BoostCall& c, const SearchArgs& a, int64_t c0, hipStream_t st);
+// vs_boost_stats' counters (a bonus search's base search counts there too).
+extern RouteStats g_boost_stats;
 
 }  // namespace host
 }  // namespace vs

@@ -788,7 +788,10 @@ hipError_t launch_where_drop(int mode, const float* Din, const int64_t* Iin, int
 // and is not in xrows[xoffs[q] .. xoffs[q + 1]) (ascending rows in place; both
 // null: no exclusions).  preds / xoffs / the floors are indexed like qaux (by
 // the query's row in Q: qlist[slot] for the GEMM, 0 .. nq - 1 for the GEMV,
-// whose preds hold kGemvMaxQ entries, `on` clear past nq).
+// whose preds hold kGemvMaxQ entries, `on` clear past nq).  The boosted scan's
+// launchers take the same arguments with specs given (indexed like preds);
+// the where scan's take them with specs null.
+struct BoostSpec;
 struct GemmWhereArgs {
   const void* X = nullptr;
   const float* xaux = nullptr;
@@ -804,6 +807,7 @@ struct GemmWhereArgs {
   const WherePred* preds = nullptr;
   const int64_t* xoffs = nullptr;
   const int64_t* xrows = nullptr;
+  const BoostSpec* specs = nullptr;
 };
 hipError_t launch_gemm_topk_where(int mode, const GemmWhereArgs& a, Partials part,
                                   hipStream_t st);
@@ -819,7 +823,9 @@ struct GemvWhereArgs {
   const WherePred* preds = nullptr;
   const int64_t* xoffs = nullptr;
   const int64_t* xrows = nullptr;
-  unsigned long long* streamed = nullptr;  // optional: += the rows the launch loaded
+  // optional: += the rows the launch loaded (the where scan only)
+  unsigned long long* streamed = nullptr;
+  const BoostSpec* specs = nullptr;
 };
 // Modes IP and L2D, nq <= kGemvMaxQ, one list per query per block (part.P ==
 // nblocks).  A 4-row step none of whose rows passes any query's predicate is
@@ -859,11 +865,11 @@ hipError_t launch_boost_rerank(int mode, const float* Din, const int64_t* Iin, i
                                bool w_is_all, float giveup, float* Dout, int64_t* Iout,
                                int* state, float* deficit, float* spread, hipStream_t st);
 // Route B: launch_gemm_topk_where / launch_gemv_topk_where with the lists, the
-// floors and the partials in final keys; specs is indexed like preds.
-hipError_t launch_gemm_topk_boost(int mode, const GemmWhereArgs& a, const BoostSpec* specs,
-                                  Partials part, hipStream_t st);
-hipError_t launch_gemv_topk_boost(int mode, int nq, const GemvWhereArgs& a,
-                                  const BoostSpec* specs, Partials part, hipStream_t st);
+// floors and the partials in final keys; a.specs must be given.
+hipError_t launch_gemm_topk_boost(int mode, const GemmWhereArgs& a, Partials part,
+                                  hipStream_t st);
+hipError_t launch_gemv_topk_boost(int mode, int nq, const GemvWhereArgs& a, Partials part,
+                                  hipStream_t st);
 
 // Bonus searches (vs_bonus.hip; vs_api_bonus.hip vs_search_bonus): exact top-k
 // by final_key = fl32(fl32(key - b) - s), s a per-(query, row) number the

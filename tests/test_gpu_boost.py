@@ -308,6 +308,49 @@ def test_random_data_with_predicates_and_exclusions(vf, normal_indexes, dtype, m
     assert "scan" in routes and routes & {"windows", "scanwindows"}
 
 
+# ---- 5b. no boost under predicates is the raw where search ------------------------------
+@pytest.fixture(scope="module")
+def pinned_indexes(vf):
+    xb, _ = _int_data(1, 4999, seed=13)
+    cols, tags = _attr_data(4999, seed=6)
+    out = {}
+    for dtype in ("f32", "bf16"):  # the rows are small integers: exact in bf16 too
+        for metric in (L2, IP):
+            index = vf.IndexFlat(DIM, metric, dtype=dtype)
+            index.add(xb)
+            out[dtype, metric] = (index, index.attributes(cols, tags))
+    return cols, tags, out
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("nq", [1, 8, 9, 33, 129])
+def test_no_boost_under_predicates_is_the_raw_where_search(vf, pinned_indexes, dtype, metric, nq):
+    """The two kinds of the shared route driver and scan kernels, pinned to each
+    other: with boost None b = +0, so fl32(key - b) is the key's own bits, and a
+    boosted search with per-query predicates and exclusions returns what
+    search_where(raw=True) returns: I equal, D bit for bit.  Once through the
+    scan (the streaming kernel at nq = 1, 8, 9, the MFMA kernel at 33, 129; k =
+    70 takes two pages and the floor) and once by the default routes."""
+    cols, tags, idx = pinned_indexes
+    index, attrs = idx[dtype, metric]
+    _, xq = _int_data(nq, 4999, seed=14)
+    # bands of mixed selectivity; 0.001 is about five rows, None passes nothing
+    where = _bands(nq, [0.3, None, 0.001, 1, 0.03], seed=15)
+    if nq >= 8:  # a property of the fixture: a query passes nothing, one fewer than 10 rows
+        counts = wo.pass_mask(cols, tags, *where, n=4999).sum(axis=1)
+        assert (counts == 0).any() and ((counts > 0) & (counts < 10)).any(), counts[:8]
+    _, I0 = index.search(xq, 8, raw=True)
+    exclude = [[int(v) for v in I0[q, :3 + q % 3]] for q in range(nq)]
+    for k in (10, 70):
+        for scan in (True, False):
+            Dw, Iw = index.search_where(xq, k, attrs, where, exclude=exclude, raw=True, scan=scan)
+            Db, Ib = index.search_boost(xq, k, attrs, None, where=where, exclude=exclude,
+                                        scan=scan)
+            np.testing.assert_array_equal(Ib, Iw)
+            np.testing.assert_array_equal(Db.view(np.uint32), Dw.view(np.uint32))
+
+
 # ---- 6. tombstones and staleness --------------------------------------------------------
 def test_tombstones_and_staleness(vf):
     n, nq = 3000, 40
